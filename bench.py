@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the proving hot path on a synthetic trace, one rank per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--workload starknet_2p20]
+    python bench.py --gpus N --steps K --warmup W [--workload starknet_2p20] [--dump-outputs DIR] [--full]
 
 A step = ONE PROOF: every GPU stage of SURVEY.md §3.1 steps 2-9 (LDE of base and
 extension columns, row hashing + Merkle trees, composition-constraint evaluation,
@@ -15,13 +15,22 @@ not depend on the trace's contents, and every stage's cost is data-independent.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks
 (torch.distributed.run, one per GPU) and prints rank 0's line; under an external launcher it runs as one rank.
-The default run (starknet_2p20, one GPU) also times the north-star's own configuration - recursive layout, 2^20 steps,
-CairoVerifierClaim - for a few proofs and reports it as `north_star` in the same line.
 
-Prints ONE JSON line on rank 0: prove wall-time (s), plus the Fp NTT rate,
-`roofline` (NTT pass kernel, HIP-event timed inside the same K proofs) and
-`cpu_baseline` (the CPU oracle — a port, not the reference binary — on a bounded
-sample of the same stages, on this box's host cores).
+Prints ONE JSON line on rank 0: prove wall-time (s), plus the Fp NTT rate and
+`roofline` (NTT pass kernel, HIP-event timed inside the same K proofs).  A plain run does
+only that: set up, warm up, time the K proofs, print.
+
+--full adds what takes runs of its own beside the headline figure: `cpu_baseline` (the CPU
+oracle — a port, not the reference binary — on a bounded sample of the same stages, on the
+host's cores), the stage clocks (one extra stamped proof), the files -> proof leg
+(`end_to_end`) and, for the default workload (starknet_2p20, one GPU), the north-star's own
+configuration - recursive layout, 2^20 steps, CairoVerifierClaim - for a few proofs as
+`north_star`; for the 64-bit field workloads, its other kernels and its CPU leg.
+
+--dump-outputs DIR writes what the last timed step computed (the proof a caller of the timed
+path receives) as DIR/<name>.npy, integers held exactly in floats: bytes as float32, 64-bit
+limbs as their two 32-bit halves in float64 (a trailing axis of 2).  The inputs are seeded:
+the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -114,6 +123,64 @@ def emit(obj):
     else:
         _REAL_STDOUT.write(line + "\n")
         _REAL_STDOUT.flush()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _exact_floats(a):
+    """an integer array as floats that hold every value exactly: 1- and 2-byte integers -> float32, 4-byte -> float64,
+    8-byte -> their two little-endian 32-bit halves in float64 (a trailing axis of 2)"""
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    if a.dtype.itemsize <= 2:
+        return a.astype(np.float32)
+    if a.dtype.itemsize == 8:
+        a = a.view(np.uint32).reshape(a.shape + (2,))
+    return a.astype(np.float64)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as `path`/<name>.npy (see _exact_floats), at most DUMP_LIMIT_BYTES in all"""
+    import numpy as np
+    out = {name: _exact_floats(a) for name, a in arrays.items() if a is not None}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def proof_outputs(p):
+    """the arrays of a proof of the C++ host (hostlib.parse_proof -> prover.Proof)"""
+    import numpy as np
+    u8 = lambda b: np.frombuffer(b, dtype=np.uint8)
+    out = {"roots": u8(p.base_root + (p.extension_root or bytes(32)) + p.composition_root),
+           "challenges": np.array(p.challenges, dtype=np.uint64).reshape(-1, 4), "composition_coeff": p.composition_coeff,
+           "z": p.z, "deep_alpha": p.deep_alpha, "ood_trace": p.ood_trace, "ood_composition": p.ood_composition,
+           "fri_alphas": np.array(p.fri_alphas, dtype=np.uint64).reshape(-1, 4), "fri_remainder": p.fri_remainder,
+           "pow_nonce": np.array([p.pow_nonce], dtype=np.uint64), "query_positions": np.array(p.query_positions, dtype=np.uint64),
+           "base_rows": p.base_rows, "extension_rows": p.extension_rows, "composition_rows": p.composition_rows,
+           "base_paths": p.base_paths, "extension_paths": p.extension_paths, "composition_paths": p.composition_paths}
+    for k, layer in enumerate(p.fri_layers):
+        out["fri%d_root" % k] = u8(layer.root)
+        out["fri%d_positions" % k] = np.array(layer.positions, dtype=np.uint64)
+        out["fri%d_rows" % k], out["fri%d_paths" % k] = layer.rows, layer.paths
+    return out
+
+
+def last_step_keeper(step, steps, keep):
+    """a step for timed_steps whose LAST call returns its result to the caller (keep[0]): step(True) there, step() before"""
+    calls = [0]
+
+    def timed():
+        calls[0] += 1
+        if calls[0] == steps:
+            keep[0] = step(True)
+        else:
+            step()
+    return timed
 
 
 def ntt_field_ops(log_size):
@@ -262,10 +329,15 @@ def bench_goldilocks(args, log_steps, rank, local_rank, world, device):
     dt = time.perf_counter() - t0
     ntt_ms, launches = ctx.profile_read(be.PROF_NTT_PASS)
     ctx.profile(False)
+    if rank == 0 and args.dump_outputs:
+        # what the last step left: the extended columns and the coefficients, a fixed seeded sample of each (2^20 values)
+        pick = torch.from_numpy(np.random.default_rng(0x44554D50).choice(ncols * (n << lb), size=1 << 20, replace=False)).to(device)
+        dump_outputs(args.dump_outputs, {"evals_sample": evals.reshape(-1)[pick].cpu().numpy(), "evals_sample_index": pick.cpu().numpy(),
+                                         "coeffs_sample": coeffs.reshape(-1)[pick % (ncols * n)].cpu().numpy()})
     # the field's other kernels on the same columns, timed beside the headline (not part of `value`): out-of-domain
     # evaluation and DEEP composition over Fq3 for a plain-layout-sized mask, then the FRI layers down to <= 16 x blowup points
     other = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         def timed(name, fn):
             fn()
             torch.cuda.synchronize()
@@ -323,7 +395,7 @@ def bench_goldilocks(args, log_steps, rank, local_rank, world, device):
                             "note": "algorithmic bytes = 2 N 8 B per transform (SURVEY 8d); a transform of 2^24 (2^25) points is "
                                     "%d (%d) passes of 16 B per element, so the kernel's own stream rate is `streamed_bytes_per_s`"
                                     % (len(_gl_passes(log_n)), len(_gl_passes(log_n + lb)))}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle_py as oracle
             sl = 20
             col = np.random.default_rng(1).integers(0, 2**62, size=1 << sl, dtype=np.uint64)
@@ -397,11 +469,14 @@ def bench_goldilocks_plain(args, log_steps, rank, local_rank, world, device):
     barrier()
     ctx.profile(True)
     ctx.profile_reset()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, gs.proof_to_arrays(last))
     kinds = [("ntt_pass", be.PROF_NTT_PASS), ("hash_rows", be.PROF_HASH_ROWS), ("merkle", be.PROF_MERKLE), ("fri_fold", be.PROF_FRI),
              ("quotient", be.PROF_QUOTIENT), ("deep", be.PROF_DEEP), ("extension_scans", be.PROF_EXT)]
     prof = {name: ctx.profile_read(k) for name, k in kinds}
@@ -581,6 +656,10 @@ def bench_sharded(args, layout, log_steps, rank, local_rank, world, device):
         host_profile = cProfile.Profile()
         host_profile.enable()
     sec = timed_steps(prove_once, args.steps, 0, barrier, all_max)
+    if rank == 0 and args.dump_outputs:
+        # the proof comes out on rank 0 in the reference's wire format: its bytes as they are
+        import numpy as np
+        dump_outputs(args.dump_outputs, {"proof_wire_bytes": np.frombuffer(wire_proof[0], dtype=np.uint8)})
     if host_profile is not None:
         import pstats
         host_profile.disable()
@@ -823,8 +902,9 @@ def end_to_end(ctx, layout, log_steps, device, repeats=5):
     return out
 
 
-def bench_proof(args, workload, rank, local_rank, world, device, steps, warmup, cpu_leg):
-    """K whole proofs of one workload through the C++ host on this rank's GPU -> the report (rank 0) or None"""
+def bench_proof(args, workload, rank, local_rank, world, device, steps, warmup, cpu_leg, main_leg=True):
+    """K whole proofs of one workload through the C++ host on this rank's GPU -> the report (rank 0) or None.  main_leg: the
+    workload the line is about (--dump-outputs writes its last proof), not the north_star leg beside it"""
     from sandstorm_amd import backend as be, extension, hostlib, public_input
     from sandstorm_amd.prover import ProofOptions
     layout, log_steps = WORKLOADS[workload]
@@ -907,15 +987,19 @@ def bench_proof(args, workload, rank, local_rank, world, device, steps, warmup, 
     barrier()
     ctx.profile(True)
     ctx.profile_reset()
-    sec_per_proof = timed_steps(step, steps, 0, barrier, all_max)
+    dump = args.dump_outputs if rank == 0 and main_leg else None
+    last = [None]
+    sec_per_proof = timed_steps(last_step_keeper(step, steps, last) if dump else step, steps, 0, barrier, all_max)
+    if dump:
+        dump_outputs(dump, proof_outputs(last[0]))
     kinds = [("ntt_pass", be.PROF_NTT_PASS), ("hash_rows", be.PROF_HASH_ROWS), ("merkle", be.PROF_MERKLE),
              ("fri_fold", be.PROF_FRI), ("quotient", be.PROF_QUOTIENT), ("deep", be.PROF_DEEP),
              ("extension_scans", be.PROF_EXT)]
     prof = {name: ctx.profile_read(k) for name, k in kinds}
-    # one more proof, untimed, with shader-clock stamps around every profiled launch (ss_profile_enable level 2: s_memtime /
+    # --full: one more proof, untimed, with shader-clock stamps around every profiled launch (ss_profile_enable level 2: s_memtime /
     # s_memrealtime read by one wave per XCD before and after each scope): the clock each stage's kernels are granted IN THIS RUN
     stage_clock = {}
-    if not args.no_stage_clocks:
+    if args.full and not args.no_stage_clocks:
         try:
             ctx.profile(2)
         except Exception as e:          # noqa: BLE001 - no stream for the clock monitor that leaves the measured one alone: the line goes without clocks
@@ -1062,7 +1146,7 @@ def bench_proof(args, workload, rank, local_rank, world, device, steps, warmup, 
         # the legs beside the measurement must not cost the line that carries it: one that fails is reported in its place
         if cpu_leg:
             out["cpu_baseline"] = _side_leg("cpu_baseline", cpu_baseline, layout, log_steps, ctx)
-        if world == 1 and not real and not args.no_end_to_end and log_steps >= 17:
+        if args.full and world == 1 and not real and not args.no_end_to_end and log_steps >= 17:
             out["end_to_end"] = _side_leg("end_to_end", end_to_end, ctx, layout, log_steps, device)
     # everything that lives in the context's pool goes before the context does
     if real:
@@ -1084,6 +1168,12 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="starknet_2p20", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, the legs that take runs of their own: the CPU baseline, the stage clocks, the files -> "
+                         "proof leg, the north_star leg of the default workload, the 64-bit field's other kernels (the --no-* options "
+                         "below skip them one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, exact)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-north-star", action="store_true", help="skip the recursive_2p20 leg of the default run")
     ap.add_argument("--no-stage-clocks", action="store_true",
@@ -1146,13 +1236,13 @@ def main():
             dist.init_process_group(backend="nccl", rank=0, world_size=1, device_id=device)
         return bench_sharded(args, layout, log_steps, rank, local_rank, world, device)
     out = bench_proof(args, args.workload, rank, local_rank, world, device, args.steps, args.warmup,
-                      cpu_leg=not args.no_cpu_baseline and world == 1)
-    if rank == 0 and world == 1 and args.workload == "starknet_2p20" and not args.no_north_star:
+                      cpu_leg=args.full and not args.no_cpu_baseline and world == 1)
+    if args.full and rank == 0 and world == 1 and args.workload == "starknet_2p20" and not args.no_north_star:
         # north_star's own target beside BASELINE's metric configuration: recursive layout, 2^20 steps, the CLI's claim for it
         # (cli/src/main.rs:95-99: FriendlyMerkleTree<22> + Cairo coin), the same protocol on fewer proofs, in the same run
         # (a leg beside BASELINE's metric: if it fails, the line that carries the metric still goes out and says so)
         ns = _side_leg("north_star", bench_proof, args, "recursive_2p20", rank, local_rank, world, device, max(10, args.steps), 2,
-                       not args.no_cpu_baseline)          # >= 10 timed proofs in a driver-style run (3 were a thin sample)
+                       not args.no_cpu_baseline, False)          # >= 10 timed proofs in a driver-style run (3 were a thin sample)
         if "error" in ns and "value" not in ns:
             out["north_star"] = {"workload": "recursive_2p20", "error": ns["error"]}
         else:

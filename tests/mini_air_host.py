@@ -20,7 +20,9 @@ def load():
         host = os.path.join(build, "libsandstorm_host.so")
         if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(SRC), os.path.getmtime(host)):
             os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", OUT, SRC, "-L" + build, "-lsandstorm_host", "-Wl,-rpath," + build])
+            # the host library found relative to this one ($ORIGIN), not by this tree's absolute path: the tree may move after the build
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", OUT, SRC, "-L" + build, "-lsandstorm_host",
+                                   "-Wl,-rpath,$ORIGIN/../../sandstorm_amd/_build"])
         _lib = C.CDLL(OUT, mode=C.RTLD_GLOBAL)
         _lib.sst_mini_air_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     return _lib

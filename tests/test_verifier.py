@@ -194,10 +194,9 @@ def test_cpp_verifier_on_the_committed_proofs():
     air2.close()
 
 
-REFERENCE_PROOF = "/root/reference/bootloader-proof.bin"
+REFERENCE_PROOF = os.path.join(GOLD, "reference_bootloader_recursive.proof")       # the reference's bootloader-proof.bin, as it is
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_PROOF), reason="the reference checkout is only mounted in the build container")
 def test_reference_proof_passes_every_check_below_the_transcript(golden):
     """The reference's own shipped recursive-layout proof through this repo's verifier, minus the transcript (its public
     input is not shipped): with the out-of-domain point and DEEP coefficient recovered from its data

@@ -6,16 +6,16 @@ import pytest
 
 from sandstorm_amd import wire
 
-REF_PROOFS = ["/root/reference/example/array-sum.proof.saved", "/root/reference/bootloader-proof.bin"]
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# the reference's shipped proof files, copied as they are (tests/golden/README.md): example/array-sum.proof.saved (starknet
+# layout) and bootloader-proof.bin (recursive layout)
+REF_PROOFS = ["reference_array_sum_starknet.proof", "reference_bootloader_recursive.proof"]
 
 
-@pytest.mark.parametrize("path", REF_PROOFS)
-def test_reference_proofs_round_trip(path):
-    """parse -> serialize reproduces the reference's shipped proof files byte for byte (the files are not copied
-    into this repo; the test runs where /root/reference is mounted)."""
-    if not os.path.exists(path):
-        pytest.skip("reference not mounted")
-    raw = open(path, "rb").read()
+@pytest.mark.parametrize("name", REF_PROOFS)
+def test_reference_proofs_round_trip(name):
+    """parse -> serialize reproduces the reference's shipped proof files byte for byte."""
+    raw = open(os.path.join(GOLD, name), "rb").read()
     p = wire.parse(raw)
     assert wire.serialize(p) == raw
     assert p.options[1] == 2 and p.options[3] == 8 and len(p.ood_composition) == 2
@@ -24,10 +24,7 @@ def test_reference_proofs_round_trip(path):
 
 
 def test_parse_matches_golden_fixture(golden):
-    path = REF_PROOFS[0]
-    if not os.path.exists(path):
-        pytest.skip("reference not mounted")
-    p = wire.parse(open(path, "rb").read())
+    p = wire.parse(open(os.path.join(GOLD, REF_PROOFS[0]), "rb").read())
     g = golden("saved_proof_openings.json")
     assert p.base_root.hex() == g["roots"]["base"] and p.extension_root.hex() == g["roots"]["extension"]
     assert [l.root.hex() for l in p.fri_layers] == g["roots"]["fri_layers"]

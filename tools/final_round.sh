@@ -7,7 +7,7 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -q --durations=8 2>&1 | tail -16 > $OUT/pytest_gpu.txt; cat $OUT/pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $OUT/smoke.txt
 for w in starknet_2p20 recursive_2p20 recursive_2p16 array_sum_example; do
-  timeout 600 python bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout 600 python bench.py --workload $w --full > $OUT/bench_$w.json 2> $OUT/bench_$w.err
   python -c "import json; d=json.load(open('$OUT/bench_$w.json')); print('$w', d['value'], d['stage_ms_per_proof'], d['ntt_gfield_ops_per_s'], d.get('cpu_baseline',{}).get('measured_sample_s'))"
 done
 timeout 300 python bench.py --workload starknet_2p20 --mode shard --sharded-host cpp --no-cpu-baseline > $OUT/bench_starknet_2p20_shard_cpp_1gpu.json 2> $OUT/bench_shard_cpp.err
@@ -19,9 +19,9 @@ tools/_build/fma_mulbench > $OUT/fma_mulbench.txt 2>&1
 timeout 300 python tools/e2e_device.py starknet recursive > $OUT/e2e_device.txt 2>&1; cat $OUT/e2e_device.txt
 (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/rp_trace && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_trace -- python $R/tools/e2e_device.py starknet recursive > /dev/null 2>&1)
 f=$(find /tmp/rp_trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && ( head -1 $f; grep -i "trace_\|mem_\|scan_chunks\|scan_sums\|scan_apply_kernel_u32" $f ) > $OUT/device_trace_kernel_stats.csv
-timeout 300 python bench.py --workload goldilocks_lde_2p20 --steps 10 --warmup 2 > $OUT/bench_goldilocks_lde_2p20.json 2> $OUT/bench_gl.err
-timeout 300 python bench.py --workload goldilocks_plain_2p20 --steps 3 --warmup 1 > $OUT/bench_goldilocks_plain_2p20.json 2> $OUT/bench_glp.err
-timeout 300 python bench.py --workload starknet_2p22 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_starknet_2p22.json 2> $OUT/bench_2p22.err
+timeout 300 python bench.py --full --workload goldilocks_lde_2p20 --steps 10 --warmup 2 > $OUT/bench_goldilocks_lde_2p20.json 2> $OUT/bench_gl.err
+timeout 300 python bench.py --full --workload goldilocks_plain_2p20 --steps 3 --warmup 1 > $OUT/bench_goldilocks_plain_2p20.json 2> $OUT/bench_glp.err
+timeout 300 python bench.py --full --workload starknet_2p22 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_starknet_2p22.json 2> $OUT/bench_2p22.err
 python -c "
 import json
 for w in ('starknet_2p20_shard_cpp_1gpu','goldilocks_lde_2p20','goldilocks_plain_2p20','starknet_2p22'):

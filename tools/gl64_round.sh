@@ -8,7 +8,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd $R
 timeout 200 python -m pytest tests/test_goldilocks.py tests/test_goldilocks_stark.py -m gpu -x -q 2>&1 | tail -8 > $OUT/pytest_gpu.txt; cat $OUT/pytest_gpu.txt
 timeout 90 python bench.py --workload goldilocks_plain_2p20 --steps 3 --warmup 1 > $OUT/bench_goldilocks_plain_2p20.json 2> $OUT/bench_glp.err
-timeout 60 python bench.py --workload goldilocks_lde_2p20 --steps 10 --warmup 2 > $OUT/bench_goldilocks_lde_2p20.json 2> $OUT/bench_gl.err
+timeout 60 python bench.py --full --workload goldilocks_lde_2p20 --steps 10 --warmup 2 > $OUT/bench_goldilocks_lde_2p20.json 2> $OUT/bench_gl.err
 python -c "
 import json
 for w in ('goldilocks_plain_2p20','goldilocks_lde_2p20'):

@@ -28,7 +28,7 @@ done
 bench xyzz_w26_2p16 recursive_2p16 SS_PED_WINDOW=26
 bench xyzz_w26_2p20 recursive_2p20 SS_PED_WINDOW=26
 # ---- the default line with the live stage clocks (no CPU legs here)
-timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
 python -c "
 import json
 d=json.load(open('$OUT/bench_default.json')); print('default', d['value'], d['stage_ms_per_proof']); print('alu', d['roofline']['alu']); print('e2e', d.get('end_to_end')); print('ns', d['north_star']['value'], d['north_star']['roofline']['alu'])" | tee $OUT/default_summary.txt

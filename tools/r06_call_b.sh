@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/r06b
 rm -rf $OUT; mkdir -p $OUT
 cd $R
 timeout 2400 python -m pytest -m gpu -q -x tests 2>&1 | tail -12 | tee $OUT/pytest_gpu.txt
-timeout 900 python bench.py --steps 10 --warmup 3 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full --steps 10 --warmup 3 > $OUT/bench_default.json 2> $OUT/bench_default.err
 python -c "
 import json
 d=json.load(open('$OUT/bench_default.json')); print('default', d['value'], d['stage_ms_per_proof']); print('e2e', json.dumps(d.get('end_to_end'))[:1500]); print('ns', d['north_star']['value'], json.dumps(d['north_star'].get('end_to_end'))[:1500])" | tee $OUT/default_summary.txt

@@ -6,9 +6,9 @@ OUT=$R/gpurun_out/r06k
 rm -rf $OUT; mkdir -p $OUT
 cd $R
 T0=$(date +%s.%N)
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 T1=$(date +%s.%N); echo "python bench.py (no flags): $(echo "$T1 - $T0" | bc) s wall" | tee $OUT/default_time.txt
-timeout 600 python bench.py --workload recursive_2p20 > $OUT/bench_recursive_2p20.json 2> $OUT/bench_recursive_2p20.err
+timeout 600 python bench.py --full --workload recursive_2p20 > $OUT/bench_recursive_2p20.json 2> $OUT/bench_recursive_2p20.err
 python - <<'PY'
 import json
 for f in ("bench_default", "bench_recursive_2p20"):
