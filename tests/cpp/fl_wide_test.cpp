@@ -5,17 +5,14 @@
 #include <cstdint>
 #include <cstdio>
 #include "../../sandstorm_amd/csrc/fl252.h"
+#include "edge_fp.h"
 
 using namespace ss;
 
 static uint64_t st = 0x9E3779B97F4A7C15ull;
 static uint64_t next() { uint64_t z = (st += 0x9E3779B97F4A7C15ull); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); }
-static Fp rand_fp() {
-    Fp a;
-    for (int i = 0; i < 8; ++i) a.v[i] = (u32)next();
-    a.v[7] &= 0x07ffffffu;                    // < 2^251 < p
-    return a;
-}
+static long draws = 0;
+static Fp rand_fp() { return edge_fp::draw(next, draws++); }     // the edge values, then edge / [2^251, p) / uniform draws of [0, p)
 
 int main() {
     int bad = 0;

@@ -5,13 +5,12 @@
 #include <random>
 
 #include "../../sandstorm_amd/csrc/fp252_host.h"
+#include "edge_fp.h"
 
 using namespace ss;
 
 static Fp canonical(std::mt19937_64 &rng, int kind) {
-    Fp a;
-    for (int i = 0; i < 8; ++i) a.v[i] = (u32)rng();
-    a.v[7] &= 0x07ffffffu;                                   // < 2^251 < p
+    Fp a = edge_fp::draw(rng, 1 << 30);                     // an edge value, a value of [2^251, p) or a uniform one of [0, p)
     if (kind == 1) a = fp_zero();
     if (kind == 2) a = fp_one();
     if (kind == 3) { a = fp_zero(); a.v[6] = SS_P6; a.v[7] = SS_P7; }                       // p - 1
@@ -24,7 +23,11 @@ int main() {
     std::mt19937_64 rng(2026);
     int bad = 0;
     for (int it = 0; it < 200000; ++it) {
-        const Fp a = canonical(rng, it < 36 ? it % 6 : 0), b = canonical(rng, it < 36 ? it / 6 : 0);
+        Fp a = canonical(rng, it < 36 ? it % 6 : 0), b = canonical(rng, it < 36 ? it / 6 : 0);
+        if (it >= 36 && it < 36 + edge_fp::N_EDGE * edge_fp::N_EDGE) {                  // every pair of edge values
+            a = edge_fp::EDGE[(it - 36) % edge_fp::N_EDGE];
+            b = edge_fp::EDGE[(it - 36) / edge_fp::N_EDGE];
+        }
         const H4 ha = h4_from_fp(a), hb = h4_from_fp(b);
         if (!fp_eq(h4_to_fp(ha), a)) ++bad;
         if (!fp_eq(h4_to_fp(h4_mul(ha, hb)), fp_mul(a, b))) { if (bad < 5) printf("mul differs at %d\n", it); ++bad; }

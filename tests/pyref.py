@@ -71,3 +71,68 @@ def interpolate_eval(xs, ys, t):
                 den = den * (xi - xj) % P
         acc = (acc + yi * num * pow(den, -1, P)) % P
     return acc
+
+
+def _bitrev(x, bits):
+    return int(format(x, "0%db" % bits)[::-1], 2) if bits else 0
+
+
+def _fft(a, w):
+    """values of the polynomial with coefficients a at w^0 .. w^(n-1), w of order n = len(a) (radix 2, recursive)"""
+    n = len(a)
+    if n == 1:
+        return list(a)
+    even, odd = _fft(a[0::2], w * w % P), _fft(a[1::2], w * w % P)
+    out, t = [0] * n, 1
+    for k in range(n // 2):
+        u = odd[k] * t % P
+        out[k], out[k + n // 2] = (even[k] + u) % P, (even[k] - u) % P
+        t = t * w % P
+    return out
+
+
+def ntt(coeffs, offset=1):
+    """natural order: value k is sum_j coeffs[j] (offset w_n^k)^j"""
+    n = len(coeffs)
+    return _fft([c * pow(offset, j, P) % P for j, c in enumerate(coeffs)], root_of_unity(n))
+
+
+def intt(values, offset=1):
+    """the inverse of ntt(., offset): the coefficients, natural order"""
+    n = len(values)
+    a = _fft(list(values), pow(root_of_unity(n), -1, P))
+    inv_n, inv_off = pow(n, -1, P), pow(offset, -1, P)
+    return [v * inv_n * pow(inv_off, j, P) % P for j, v in enumerate(a)]
+
+
+def horner(coeffs, x):
+    acc = 0
+    for c in reversed(coeffs):
+        acc = (acc * x + c) % P
+    return acc
+
+
+def fri_fold(evals, fold, alpha, offset, bitrev_rows=False, unnormalised=False):
+    """fri.hip's header formula: row j holds f at x_j w_fold^k, k < fold, and folds to
+    (1/fold) sum_m (alpha / x_j)^m sum_k f(x_j w_fold^k) w_fold^(-k m)  (no 1/fold when unnormalised).
+    Natural order: f(x_j w_fold^k) = evals[j + k rows], x_j = offset w^j.  Bit-reversed rows: row r = evals[fold r .. fold r + fold),
+    entry i at x_r w_fold^bitrev(i), x_r = offset w^bitrev(r); the output is in bit-reversed order too."""
+    n = len(evals)
+    rows, log_fold = n // fold, fold.bit_length() - 1
+    w, wf_inv = root_of_unity(n), pow(root_of_unity(fold), -1, P)
+    scale = 1 if unnormalised else pow(fold, -1, P)
+    out = []
+    for j in range(rows):
+        if bitrev_rows:
+            x = offset * pow(w, _bitrev(j, (rows.bit_length() - 1)), P) % P
+            v = [evals[fold * j + _bitrev(k, log_fold)] for k in range(fold)]
+        else:
+            x = offset * pow(w, j, P) % P
+            v = [evals[j + k * rows] for k in range(fold)]
+        t = alpha * pow(x, -1, P) % P
+        acc = 0
+        for m in range(fold):
+            s = sum(v[k] * pow(wf_inv, k * m, P) for k in range(fold)) % P
+            acc = (acc + s * scale * pow(t, m, P)) % P
+        out.append(acc)
+    return out

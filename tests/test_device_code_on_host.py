@@ -63,6 +63,13 @@ def test_sweeps_over_the_sizes_the_gpu_suite_samples(emulated_library):
     assert "70 passed" in out, out[-500:]                     # 61 sweeps + DEEP masks on the kernels' bookkeeping boundaries (both fields) + 40 random programs
 
 
+def test_edge_values_at_the_top_of_the_field(emulated_library):
+    """tests/test_gpu_edge_values.py: the 252-bit kernels on inputs in [2^251, p), p - 1, the Montgomery images of +-1 ... and on
+    outputs forced onto them - the lazy bounds' edge cases, which random_column's draws (all below 2^251) never reach"""
+    out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_edge_values.py", "-k", "not large"])
+    assert "77 passed" in out, out[-500:]                     # all but the 2^19 / 2^20 transforms and the 2^19-point constraint kernels
+
+
 def test_the_64_bit_field(emulated_library):
     """tests/test_goldilocks.py below the benchmark sizes, every transform size (tests/hipemu/extra_gl64_sizes.py), and a whole proof
     of the plain layout equal to the one the MI355X wrote, and one under the SHA-256 claim (tests/hipemu/extra_gl64_proof.py)"""
