@@ -510,7 +510,9 @@ enum { SS_TRACE_ERR_MISSING_CELL = 1,        /* the run reads a cell memory.bin 
        SS_TRACE_ERR_NO_ONES = 256,           /* memory does not start at address 1                                   */
        SS_TRACE_ERR_NOT_SINGLE_VALUED = 512, SS_TRACE_ERR_NOT_CONTINUOUS = 1024,      /* utils.rs:132-150            */
        SS_TRACE_ERR_TOO_MANY_GAPS = 2048,    /* more unaccessed addresses than cycles to hold them (trace.rs:594-625) */
-       SS_TRACE_ERR_FILL = 4096 };           /* the ordered accesses do not fill the column                          */
+       SS_TRACE_ERR_FILL = 4096,             /* the ordered accesses do not fill the column                          */
+       SS_TRACE_ERR_PEDERSEN_INFINITY = 8192,  /* ss_trace_pedersen: a partial sum meets its constant point (see there) */
+       SS_TRACE_ERR_PEDERSEN_INSTANCE = 16384 }; /* ss_trace_pedersen: an instance's index is beyond the blocks, or an input has a bit from 252 up: skipped */
 /* memory.bin on the device: d_records = the file's bytes (n_records x (u64 address, 32-byte little-endian word), uploaded by
  * the caller) -> d_image[address] as 4 x u64; cells the file does not name are marked (all-ones: not a field element).
  * cells: entries of d_image; records beyond it are dropped (no address above n / 2 can be accessed by a valid run). */
@@ -535,6 +537,33 @@ enum { SS_TRACE_CELL_VALUE = 0, SS_TRACE_CELL_ADDRESS = 1 };
 ss_status ss_trace_builtin(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, const ss_trace_cell *d_cells, uint32_t n_cells, const uint64_t *d_values,
                            uint32_t n_templates, const uint32_t *d_template_of_block, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin,
                            uint64_t addr_per_block, uint32_t *d_pool_addr);
+/* A GIVEN Pedersen instance's cells from its two inputs, computed on the device (builtins/src/pedersen/mod.rs:81-163; starknet
+ * trace.rs:304-386, recursive 300-400) - no template, 72 bytes per instance.  d_instances: n_given records of 9 u64 = index, a[4],
+ * b[4] (canonical little-endian limbs, both below 2^252); instance `index` owns rows [index * block_rows, (index + 1) * block_rows)
+ * of the columns (col_rows felts each; n_blocks * block_rows <= col_rows).  For each of the 512 steps j - the bits of a, then of b -
+ * row off_* + row_stride * j of the block gets the partial sum before the step (col_x, col_y), the suffix input >> (j mod 256)
+ * (col_suffix) and the slope of the step's addition (col_slope; zero where the bit is clear); then, per input, the cells
+ * bit251 && bit196 (col_flag2, off_flag2) and bit251 && bit196 && bit192 (col_flag3, off_flag3) - the second input's 256 *
+ * row_stride rows further down - and the three memory-pool pairs (addr_begin + 3 * index + k, value) for a, b and the hash at rows
+ * off_input0 / off_input1 / off_output (even) of col_pool, their integer addresses in d_pool_addr[row / 2] (col_rows / 2 u32).
+ * All values Montgomery felts, bit-identical to the host generator's.  Call it AFTER ss_trace_builtin has written the dummy
+ * instance's template over all blocks: it overwrites the given ones.  The indices must be distinct.
+ * Refused with an error (nothing launched): NULL pointers (also with n_given = 0), blocks that do not fit the columns, a column
+ * >= ncols, a cell that leaves its block.  Found on the device, as bits of d_status: an index >= n_blocks or an input with a bit
+ * from 252 up - the instance is skipped, nothing is written for it (SS_TRACE_ERR_PEDERSEN_INSTANCE); a partial sum that meets its
+ * constant point, where the chord's slope does not exist (SS_TRACE_ERR_PEDERSEN_INFINITY: no input is known to reach it; the
+ * instance's cells are then unfinished - its step-511 suffix cell holds all ones, no field element - and the caller must refuse
+ * the generation - host/device_trace.hpp does, with the host generator's "point at infinity in a Pedersen partial sum"; the tangent
+ * case, which the host generator could still trace, is refused too). */
+typedef struct {
+    uint32_t col_x, off_x, col_y, off_y, col_suffix, off_suffix, col_slope, off_slope;   /* step j: row off + row_stride * j */
+    uint32_t row_stride;                                                                  /* 1 starknet, 4 recursive */
+    uint32_t col_flag2, off_flag2, col_flag3, off_flag3;                                  /* + 256 * row_stride for the second input */
+    uint32_t col_pool, off_input0, off_input1, off_output;                                /* the three (address, value) pairs */
+} ss_trace_pedersen_layout;
+ss_status ss_trace_pedersen(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_pedersen_layout *layout,
+                            const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr,
+                            uint32_t *d_status);
 /* The 16-bit range-check pool (utils.rs:357-380; starknet trace.rs:142-165, 246-292, 388-426).  The caller counts the pool's
  * values (65536 bins: the instructions' offsets, the builtin's parts) and hands over
  *   d_first[j], j <= rc_hi - rc_lo + 1: ordered values before value rc_lo + j (every value of [rc_lo, rc_hi] max(count, 1) times),

@@ -159,6 +159,7 @@ struct ss_ctx {
         return SS_OK;
     }
     PedersenTables *ped = nullptr;
+    Fp *trace_ped_points = nullptr;         // ss_trace_pedersen: P0 and the builtin's 2 x 252 constant points
     void *scratch = nullptr;                // grow-only device scratch
     size_t scratch_bytes = 0;
     uint64_t *d_small = nullptr;            // 64 x u64: PoW prefix/best etc.
@@ -533,6 +534,7 @@ void ss_ctx_destroy(ss_ctx *ctx) {
     ctx->pool_trim();
     for (auto &kv : ctx->pool_live) hipFree(kv.first);     // leaked by the caller
     pedersen_tables_destroy(ctx->ped);
+    if (ctx->trace_ped_points) hipFree(ctx->trace_ped_points);
     ctx->monitor_stop();
     for (hipEvent_t ev : ctx->copy_events) if (ev) (void)hipEventDestroy(ev);
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
@@ -1398,7 +1400,8 @@ ss_status ss_affine_apply(ss_ctx *ctx, const uint64_t *d_maps, uint64_t count, c
 namespace {
 static_assert(SS_TRACE_ERR_MISSING_CELL == TRACE_ERR_MISSING_CELL && SS_TRACE_ERR_FILL == TRACE_ERR_FILL && SS_TRACE_ERR_NOT_CONTINUOUS == TRACE_ERR_NOT_CONTINUOUS &&
               SS_TRACE_ERR_PUBLIC_CELLS == TRACE_ERR_PUBLIC_CELLS && SS_TRACE_STATUS_WORDS == TRACE_ST_WORDS && SS_TRACE_NPC_OP1 == TRACE_NPC_OP1 &&
-              SS_TRACE_RC_OFF_OP1 == TRACE_RC_OFF_OP1 && SS_TRACE_AUX_RES == TRACE_AUX_RES && SS_TRACE_CELL_ADDRESS == TRACE_TILE_ADDRESS,
+              SS_TRACE_RC_OFF_OP1 == TRACE_RC_OFF_OP1 && SS_TRACE_AUX_RES == TRACE_AUX_RES && SS_TRACE_CELL_ADDRESS == TRACE_TILE_ADDRESS &&
+              SS_TRACE_ERR_PEDERSEN_INFINITY == TRACE_ERR_PEDERSEN_INFINITY && SS_TRACE_ERR_PEDERSEN_INSTANCE == TRACE_ERR_PEDERSEN_INSTANCE,
               "the header's constants are the kernels'");
 bool trace_layout_ok(const ss_trace_layout *l) {
     if (!l) return false;
@@ -1448,6 +1451,40 @@ ss_status ss_trace_builtin(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols,
     ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
     HIP_TRY(launch_trace_tile(ctx->stream, cp, ncols, (const TraceTileEntry *)d_cells, n_cells, (const Fp *)d_values, n_templates, d_template_of_block, n_blocks,
                               block_rows, addr_begin, addr_per_block, d_pool_addr));
+    return SS_OK;
+}
+ss_status ss_trace_pedersen(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_pedersen_layout *layout,
+                            const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr,
+                            uint32_t *d_status) {
+    if (!ctx || !d_cols || !layout || !d_pool_addr || !d_status || (n_given && !d_instances)) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!ncols || ncols > (uint32_t)MAX_COLS) return fail(SS_ERR_INVALID, "ncols out of range");
+    if (!n_blocks || !block_rows || (block_rows & 1) || col_rows > (1ull << 32) || block_rows > col_rows || n_blocks > col_rows / block_rows)
+        return fail(SS_ERR_INVALID, "the blocks do not fit the columns");
+    if (n_given > n_blocks || n_given > 0x7fffffffull) return fail(SS_ERR_INVALID, "more instances than blocks (or than one launch has workgroups)");
+    static_assert(sizeof(ss_trace_pedersen_layout) == sizeof(TracePedersenLayout), "ss_trace_pedersen_layout is TracePedersenLayout");
+    TracePedersenLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (L.col_x >= ncols || L.col_y >= ncols || L.col_suffix >= ncols || L.col_slope >= ncols || L.col_flag2 >= ncols || L.col_flag3 >= ncols || L.col_pool >= ncols)
+        return fail(SS_ERR_INVALID, "a column beyond ncols");
+    const uint64_t span = 511ull * L.row_stride, second = 256ull * L.row_stride;
+    if (!L.row_stride || L.off_x + span >= block_rows || L.off_y + span >= block_rows || L.off_suffix + span >= block_rows || L.off_slope + span >= block_rows ||
+        L.off_flag2 + second >= block_rows || L.off_flag3 + second >= block_rows)
+        return fail(SS_ERR_INVALID, "a cell leaves its block");
+    for (uint32_t off : {L.off_input0, L.off_input1, L.off_output})
+        if ((off & 1) || off + 1ull >= block_rows) return fail(SS_ERR_INVALID, "a memory-pool pair starts at an even row inside the block");
+    ColPtrs cp{};
+    for (uint32_t c = 0; c < ncols; ++c) { if (!d_cols[c]) return fail(SS_ERR_INVALID, "NULL column"); cp.dst[c] = d_cols[c]; }
+    if (!n_given) return SS_OK;
+    if (!ctx->trace_ped_points) {                                   // P0 and the 2 x 252 constant points: once per context
+        const size_t bytes = (size_t)TRACE_PEDERSEN_POINTS * 2 * sizeof(Fp);
+        void *p = nullptr;
+        HIP_TRY(ctx->malloc_retry(&p, bytes));
+        hipError_t e = hipMemcpyAsync(p, pedersen_step_points_host(), bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
+        ctx->trace_ped_points = (Fp *)p;
+    }
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_pedersen(ctx->stream, cp, L, d_instances, n_given, n_blocks, block_rows, addr_begin, ctx->trace_ped_points, d_pool_addr, d_status));
     return SS_OK;
 }
 namespace {

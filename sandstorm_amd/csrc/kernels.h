@@ -77,6 +77,9 @@ hipError_t launch_pedersen_felt_pairs(hipStream_t st, const PedersenTables *t, c
 
 // host-side hash for the Fiat-Shamir coin (Montgomery felts)
 Fp pedersen_hash_host(const Fp &a, const Fp &b);
+// the points the Pedersen BUILTIN's partial sums are made of (trace.hip): P0, then 2^i P_{1+2e} / 2^(i-248) P_{2+2e} for bit i < 252 of
+// input e - 1 + 2 * 252 affine points as (x, y) Montgomery felts, made once per process on the host
+const Fp *pedersen_step_points_host();
 
 // ---- fri.hip
 // rows row0 .. row0 + count of the layer, entry k of row row0 + i at evals[i + k * count] (the whole layer: 0, len / fold)
@@ -161,7 +164,8 @@ struct TraceMemoryArgs {
 enum { TRACE_ST_ERRORS = 0, TRACE_ST_WHERE = 1, TRACE_ST_ZEROS = 2, TRACE_ST_ONES = 3, TRACE_ST_TOP = 4, TRACE_ST_NLOW = 5, TRACE_ST_GAPS = 6, TRACE_ST_WORDS = 16 };
 enum { TRACE_ERR_MISSING_CELL = 1, TRACE_ERR_NOT_INSTRUCTION = 2, TRACE_ERR_BAD_OP1_SOURCE = 4, TRACE_ERR_BAD_RES_LOGIC = 8, TRACE_ERR_NOT_AN_ADDRESS = 16,
        TRACE_ERR_ADDRESS_RANGE = 32, TRACE_ERR_PUBLIC_ZERO = 64, TRACE_ERR_PUBLIC_CELLS = 128, TRACE_ERR_NO_ONES = 256, TRACE_ERR_NOT_SINGLE_VALUED = 512,
-       TRACE_ERR_NOT_CONTINUOUS = 1024, TRACE_ERR_TOO_MANY_GAPS = 2048, TRACE_ERR_FILL = 4096 };
+       TRACE_ERR_NOT_CONTINUOUS = 1024, TRACE_ERR_TOO_MANY_GAPS = 2048, TRACE_ERR_FILL = 4096, TRACE_ERR_PEDERSEN_INFINITY = 8192,
+       TRACE_ERR_PEDERSEN_INSTANCE = 16384 };
 hipError_t launch_trace_memory_image(hipStream_t st, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells);
 hipError_t launch_trace_cpu(hipStream_t st, const TraceLayout &L, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells,
                             const Fp &pad_value, uint64_t rc_fill, Fp *flags, Fp *npc, Fp *rc, Fp *aux, uint32_t *d_pool_addr, uint32_t *d_status);
@@ -174,6 +178,17 @@ hipError_t launch_trace_runs(hipStream_t st, Fp *col, uint64_t stride, uint64_t 
                              bool diluted);
 hipError_t launch_trace_patch(hipStream_t st, Fp *col, uint64_t col_rows, const uint64_t *d_rows, const uint64_t *d_values, uint64_t count);
 uint64_t trace_memory_scratch_words(uint64_t half);
+// a Pedersen instance's cells from its two inputs (= ss_trace_pedersen_layout): step j of the 512 at row off_* + row_stride * j of its
+// block, the two flag cells per input (the second input's 256 * row_stride further down), the three memory-pool pairs
+struct TracePedersenLayout {
+    uint32_t col_x, off_x, col_y, off_y, col_suffix, off_suffix, col_slope, off_slope, row_stride;
+    uint32_t col_flag2, off_flag2, col_flag3, off_flag3, col_pool, off_input0, off_input1, off_output;
+};
+// points: TRACE_PEDERSEN_POINTS affine points, Montgomery (x, y): the shift point P0, then the constant point of bit i of input e at
+// 1 + 252 e + i (pedersen_step_points_host)
+static constexpr uint32_t TRACE_PEDERSEN_POINTS = 1 + 2 * 252;
+hipError_t launch_trace_pedersen(hipStream_t st, const ColPtrs &cols, const TracePedersenLayout &L, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks,
+                                 uint64_t block_rows, uint64_t addr_begin, const Fp *d_points, uint32_t *d_pool_addr, uint32_t *d_status);
 hipError_t launch_trace_ordered_memory(hipStream_t st, const TraceMemoryArgs &m, uint32_t *scratch);
 
 // ---- goldilocks.hip (the 64-bit field variant)

@@ -152,6 +152,18 @@ static void build_bit_points(std::vector<Aff> &out) {
     batch_to_affine(jac, out);
 }
 
+const Fp *pedersen_step_points_host() {
+    static std::vector<Fp> flat;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        std::vector<Aff> bits;
+        build_bit_points(bits);
+        flat.push_back(canon_to_mont(PED_CANON[0][0])); flat.push_back(canon_to_mont(PED_CANON[0][1]));
+        for (const Aff &p : bits) { flat.push_back(p.x); flat.push_back(p.y); }
+    });
+    return flat.data();
+}
+
 static size_t ped_table_bytes(uint32_t W) {
     const uint64_t nwin = (PED_BITS + W - 1) / W, span = (1ull << W) - 1ull;
     return (size_t)(2ull * nwin * span * sizeof(Aff));

@@ -13,6 +13,8 @@
 //                         integers for the sort-free ordered memory below
 //   trace_tile_kernel     a builtin's instances: ONE template of cells per distinct instance (the dummy instance: one for
 //                         the whole run), written into every block that holds it; address cells are affine in the block
+//   trace_pedersen_*      the GIVEN Pedersen instances from their two inputs (72 bytes each instead of a 66 KB template): the
+//                         partial sums as one chain of Jacobian additions with one inversion per instance, then one lane per row
 //   trace_rc_*            the range-check builtin's parts and the pool's ordered values / padding (utils.rs:357-380):
 //                         runs located by binary search in a prefix array of the 65536-bin histogram
 //   trace_runs_kernel     the diluted pool's ordered column the same way
@@ -204,6 +206,153 @@ __global__ __launch_bounds__(256) void trace_tile_kernel(ColPtrs cols, u32 ncols
         v = load_fp(&values[(u64)tm * n_e + e]);
     }
     store_fp(&col_ptr[en.col][row], v);
+}
+
+// ------------------------------------------------------------------------------------------------ Pedersen instances from their inputs
+// A GIVEN Pedersen instance (index, a, b: 9 u64) -> the cells the host generator's Pedersen section writes for it
+// (host/trace_common.hpp element_steps): the 512 partial sums P0 + sum of the constant points of the set bits, the suffixes
+// input >> j, the slopes of the additions, the flag cells and the three memory-pool pairs.  Two kernels:
+//   trace_pedersen_sums_kernel   one lane per instance walks the set bits of a, then b, as ONE chain of Jacobian mixed additions
+//                                and parks (X3, Y3, H, R) of every addition in the four cells of ITS OWN row (x, y, suffix, slope of
+//                                step j: the instance's cells are the scratch).  Z3 = Z1 H, so the Z's are the prefix products of
+//                                the H's: ONE inversion of the last Z and a walk back (1 / Z_{k-1} = H_k / Z_k) turn every row into
+//                                the affine sum AFTER step j and the slope R / Z3 of step j.
+//   trace_pedersen_rows_kernel   one workgroup per instance, one lane per step: reads the sum BEFORE its step (the row of the last set
+//                                bit below it, or P0) and its own slope, barrier, writes its row - x, y, suffix, slope - then the flag
+//                                cells and the pool pairs (the last writes of the section, as on the host).
+// The exceptional case - a partial sum that meets its constant point (H = 0) - sets TRACE_ERR_PEDERSEN_INFINITY and leaves the
+// generation refused: the rows kernel does not touch that instance (its step-511 suffix cell keeps the all-ones mark, no field element); an instance whose index is beyond the blocks or whose input has a bit from 252 up (not a field element) is
+// skipped with TRACE_ERR_PEDERSEN_INSTANCE: nothing is written outside the columns.
+constexpr u32 PED_STEPS = 512, PED_INPUT_BITS = 252;
+struct PedCells { Fp *x, *y, *suffix, *slope; u64 stride; };
+__device__ __forceinline__ PedCells ped_cells(const ColPtrs &cols, const TracePedersenLayout &L, u64 base) {
+    PedCells c;
+    c.x = (Fp *)cols.dst[L.col_x] + base + L.off_x; c.y = (Fp *)cols.dst[L.col_y] + base + L.off_y;
+    c.suffix = (Fp *)cols.dst[L.col_suffix] + base + L.off_suffix; c.slope = (Fp *)cols.dst[L.col_slope] + base + L.off_slope;
+    c.stride = L.row_stride;
+    return c;
+}
+__device__ __forceinline__ bool ped_instance_ok(const u64 *rec, u64 n_blocks) { return rec[0] < n_blocks && !(rec[4] >> 60) && !(rec[8] >> 60); }
+
+__global__ __launch_bounds__(64) void trace_pedersen_sums_kernel(ColPtrs cols, TracePedersenLayout L, const u64 *__restrict__ inst, u64 n_given, u64 n_blocks,
+                                                                 u64 block_rows, const Fp *__restrict__ points, u32 *status) {
+    const u64 g = (u64)blockIdx.x * 64 + threadIdx.x;
+    if (g >= n_given) return;
+    const u64 *rec = inst + 9 * g;                                   // (the words are read where they are used: no indexed private array)
+    if (!ped_instance_ok(rec, n_blocks)) { status_error(status, TRACE_ERR_PEDERSEN_INSTANCE, g); return; }
+    const u64 index = rec[0];
+    const PedCells c = ped_cells(cols, L, index * block_rows);
+    // the suffix cell of step 511 (bit 255 of b: never set, so never scratch) says whether the chain came through: all ones - no field
+    // element - from here until the walk back is done; the rows kernel leaves an instance alone whose mark is still there
+    Fp *const mark = &c.suffix[(u64)(PED_STEPS - 1) * c.stride];
+    Fp unfinished;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) unfinished.v[k] = 0xffffffffu;
+    store_fp(mark, unfinished);
+    Fp X = load_fp(&points[0]), Y = load_fp(&points[1]), Z = fp_one();
+    bool any = false;
+    for (u32 wi = 0; wi < 8; ++wi) {                                 // the words of a, then of b, bits ascending
+        u64 bits = rec[1 + wi];
+        const u32 e = wi >> 2, bit0 = (wi & 3) * 64;
+        while (bits) {
+            const u64 low = bits & (~bits + 1);
+            bits ^= low;
+            const u32 i = bit0 + 63 - (u32)__clzll((long long)low);
+            const Fp *q = &points[2 * (1 + PED_INPUT_BITS * e + i)];
+            const Fp zz = fp_sqr(Z);
+            const Fp h = fp_sub(fp_mul(load_fp(q), zz), X), r = fp_sub(fp_mul(load_fp(q + 1), fp_mul(Z, zz)), Y);
+            if (fp_is_zero(h)) { status_error(status, TRACE_ERR_PEDERSEN_INFINITY, index); return; }
+            const Fp hh = fp_sqr(h), hhh = fp_mul(h, hh), v = fp_mul(X, hh);
+            const Fp x3 = fp_sub(fp_sub(fp_sqr(r), hhh), fp_dbl(v));
+            Y = fp_sub(fp_mul(r, fp_sub(v, x3)), fp_mul(Y, hhh));
+            X = x3;
+            Z = fp_mul(Z, h);
+            const u64 row = (u64)(256 * e + i) * c.stride;
+            store_fp(&c.x[row], X); store_fp(&c.y[row], Y); store_fp(&c.suffix[row], h); store_fp(&c.slope[row], r);
+            any = true;
+        }
+    }
+    if (!any) { store_fp(mark, fp_zero()); return; }
+    Fp zinv = fp_inv_safegcd(Z);                                     // no H was zero: Z is not
+    for (u32 wk = 8; wk-- > 0;) {                                    // the same bits, descending
+        u64 bits = rec[1 + wk];
+        const u32 e = wk >> 2, bit0 = (wk & 3) * 64;
+        while (bits) {
+            const u32 b = 63 - (u32)__clzll((long long)bits);
+            bits ^= 1ull << b;
+            const u64 row = (u64)(256 * e + bit0 + b) * c.stride;
+            const Fp zi2 = fp_sqr(zinv);
+            store_fp(&c.x[row], fp_mul(load_fp(&c.x[row]), zi2));
+            store_fp(&c.y[row], fp_mul(load_fp(&c.y[row]), fp_mul(zi2, zinv)));
+            store_fp(&c.slope[row], fp_mul(load_fp(&c.slope[row]), zinv));
+            zinv = fp_mul(zinv, load_fp(&c.suffix[row]));
+        }
+    }
+    store_fp(mark, fp_zero());
+}
+
+// the highest set bit below position `limit` (<= 512) of the chain a (bits 0 .. 255), b (256 .. 511); -1: none
+__device__ __forceinline__ int ped_last_set_below(const u64 *words /* 8 */, u32 limit) {
+    for (u32 wk = 8; wk-- > 0;) {
+        if (64 * wk >= limit) continue;
+        u64 m = words[wk];
+        if (limit - 64 * wk < 64) m &= (1ull << (limit - 64 * wk)) - 1;
+        if (m) return (int)(64 * wk + 63 - (u32)__clzll((long long)m));
+    }
+    return -1;
+}
+__device__ __forceinline__ void ped_pool_pair(Fp *pool, u32 *pool_addr, u64 row, u64 addr, const Fp &value) {
+    store_fp(&pool[row], fp_from_u64(addr));
+    store_fp(&pool[row + 1], value);
+    pool_addr[row >> 1] = sat32(addr);
+}
+__global__ __launch_bounds__(PED_STEPS) void trace_pedersen_rows_kernel(ColPtrs cols, TracePedersenLayout L, const u64 *__restrict__ inst, u64 n_blocks, u64 block_rows,
+                                                                        u64 addr_begin, const Fp *__restrict__ points, u32 *__restrict__ pool_addr) {
+    __shared__ u64 rec[9];
+    const u32 t = threadIdx.x;
+    if (t < 9) rec[t] = inst[9 * (u64)blockIdx.x + t];
+    __syncthreads();
+    if (!ped_instance_ok(rec, n_blocks)) return;                     // (flagged by the sums kernel; the whole workgroup leaves)
+    const u64 base = rec[0] * block_rows;
+    const PedCells c = ped_cells(cols, L, base);
+    const u64 *words = rec + 1;
+    {                                                                // the sums kernel's mark (every lane reads the same cell: the whole workgroup leaves)
+        const Fp m = load_fp(&c.suffix[(u64)(PED_STEPS - 1) * c.stride]);
+        if ((m.v[0] & m.v[7]) == 0xffffffffu) return;                // the chain met its constant point: the cells stay unfinished, the mark with them
+    }
+    const u32 e = t >> 8, i = t & 255;
+    const int before = ped_last_set_below(words, t);
+    const Fp x = before < 0 ? load_fp(&points[0]) : load_fp(&c.x[(u64)before * c.stride]);
+    const Fp y = before < 0 ? load_fp(&points[1]) : load_fp(&c.y[(u64)before * c.stride]);
+    const bool set = (words[4 * e + (i >> 6)] >> (i & 63)) & 1;
+    const Fp slope = set ? load_fp(&c.slope[(u64)t * c.stride]) : fp_zero();
+    Fp out = fp_zero();                                              // the sum after the last step: the hash (lane 511 keeps it)
+    if (t == PED_STEPS - 1) { const int last = ped_last_set_below(words, PED_STEPS); out = last < 0 ? load_fp(&points[0]) : load_fp(&c.x[(u64)last * c.stride]); }
+    u64 sfx[4];                                                      // input e >> i
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+        const u32 w = k + (i >> 6), sh = i & 63;
+        u64 v = w < 4 ? words[4 * e + w] >> sh : 0;
+        if (sh && w + 1 < 4) v |= words[4 * e + w + 1] << (64 - sh);
+        sfx[k] = v;
+    }
+    const Fp suffix = fp_to_mont(fp_of_words(sfx));
+    __syncthreads();
+    const u64 row = (u64)t * c.stride;
+    store_fp(&c.x[row], x); store_fp(&c.y[row], y); store_fp(&c.suffix[row], suffix); store_fp(&c.slope[row], slope);
+    __syncthreads();
+    // the flag cells (they overwrite what the steps wrote there) and the pool's pairs
+    if (t < 2) {
+        const u64 top = words[4 * t + 3];                            // bits 192 ..: bit 251 = 59, 196 = 4, 192 = 0
+        const bool f2 = ((top >> 59) & 1) && ((top >> 4) & 1), f3 = f2 && (top & 1);
+        const u64 second = (u64)t * 256 * c.stride;
+        store_fp((Fp *)cols.dst[L.col_flag2] + base + L.off_flag2 + second, fp_from_u64(f2));
+        store_fp((Fp *)cols.dst[L.col_flag3] + base + L.off_flag3 + second, fp_from_u64(f3));
+    }
+    Fp *pool = (Fp *)cols.dst[L.col_pool];
+    const u64 addr0 = addr_begin + 3 * rec[0];
+    if (t == 2 || t == 3) ped_pool_pair(pool, pool_addr, base + (t == 2 ? L.off_input0 : L.off_input1), addr0 + (t - 2), fp_to_mont(fp_of_words(words + 4 * (t - 2))));
+    if (t == PED_STEPS - 1) ped_pool_pair(pool, pool_addr, base + L.off_output, addr0 + 2, out);
 }
 
 // ------------------------------------------------------------------------------------------------ range-check builtin and pool
@@ -503,6 +652,13 @@ hipError_t launch_trace_tile(hipStream_t st, const ColPtrs &cols, u32 ncols, con
     if (!nblocks || !n_entries) return hipSuccess;
     hipLaunchKernelGGL(trace_tile_kernel, grid_for(nblocks * n_entries, 256), dim3(256), 0, st, cols, ncols, d_entries, n_entries, d_values, n_templates,
                        d_tmpl_of_block, nblocks, step, addr_begin, addr_mult, d_pool_addr);
+    return hipGetLastError();
+}
+hipError_t launch_trace_pedersen(hipStream_t st, const ColPtrs &cols, const TracePedersenLayout &L, const u64 *d_instances, u64 n_given, u64 n_blocks, u64 block_rows,
+                                 u64 addr_begin, const Fp *d_points, u32 *d_pool_addr, u32 *d_status) {
+    if (!n_given) return hipSuccess;
+    hipLaunchKernelGGL(trace_pedersen_sums_kernel, grid_for(n_given, 64), dim3(64), 0, st, cols, L, d_instances, n_given, n_blocks, block_rows, d_points, d_status);
+    hipLaunchKernelGGL(trace_pedersen_rows_kernel, dim3((u32)n_given), dim3(PED_STEPS), 0, st, cols, L, d_instances, n_blocks, block_rows, addr_begin, d_points, d_pool_addr);
     return hipGetLastError();
 }
 hipError_t launch_trace_rc_builtin(hipStream_t st, const TraceRcPlan &p, const u64 *d_given, const uint16_t *d_padding, Fp *rc, Fp *npc, u32 *d_pool_addr) {

@@ -93,3 +93,20 @@ def starknet_example(log_steps=17):
     spi = sk.example_public_input(pi)
     new_base = spi.memory_segments["poseidon"][0] + 6 * (pi.n_steps // sk.POSEIDON_RATIO)
     return states, _move_heap(memory, new_base), spi
+
+
+def pedersen_slots(layout, log_steps):
+    """Pedersen builtin instances a 2^log_steps-step trace of `layout` has room for"""
+    from sandstorm_amd.layouts import recursive as rec, starknet as sk
+    return (1 << log_steps) // (sk.PEDERSEN_BUILTIN_RATIO if layout == "starknet" else rec.PEDERSEN_BUILTIN_RATIO)
+
+
+def seeded_pedersen_instances(slots, seed=SEED0):
+    """`slots` distinct Pedersen instances (index, a, b), one per slot, as air-private-input.json's `pedersen` rows: a, b < 2^251 from
+    SplitMix64.  The example program does not touch the builtin's segment, so any inputs make a valid statement: a run whose Pedersen
+    slots are all REAL instances (the device generator's worst case) instead of the dummy one"""
+    raw = splitmix64_stream(seed ^ 0x504544, 8 * slots).reshape(slots, 8).copy()
+    raw[:, 3] &= np.uint64((1 << 59) - 1)
+    raw[:, 7] &= np.uint64((1 << 59) - 1)
+    word = lambda r, k: sum(int(r[k + j]) << (64 * j) for j in range(4))
+    return [(i, word(raw[i], 0), word(raw[i], 4)) for i in range(slots)]

@@ -5,6 +5,8 @@
 // cells go:
 //   * a section's per-instance cells are written through a Sink - HostSink stores into the host columns (the host generator),
 //     TemplateSink records them as ONE template per DISTINCT instance, which the device copies into every block that holds it;
+//   * the Pedersen builtin's GIVEN instances are the exception: the device backend uploads their inputs (72 bytes each) and
+//     ss_trace_pedersen makes their cells on the device - only the dummy instance is a template (DeviceTrace::pedersen);
 //   * DeviceTrace uploads the raw files, plans and templates and launches the kernels in the order the host sections run
 //     (a later section overwrites an earlier one's cells, as on the host); the input's errors come back as status bits and are
 //     thrown with the host generator's messages.
@@ -104,6 +106,8 @@ template <class Inst> std::map<uint32_t, const Inst *> instances_by_index(const 
 // ---- what both layouts' builtin sections share
 // a Pedersen instance's 512 curve steps and its hash (builtins/src/pedersen/mod.rs:81-163), with the reference's own assert
 struct PedersenTrace { std::vector<Step> steps; Felt out; };
+// the refusal of an instance whose steps, made from its inputs' bits, do not add up to pedersen(a mod p, b mod p): an input >= p
+constexpr const char *PEDERSEN_NOT_THE_HASH = "Pedersen partial sums do not end at the hash";
 inline std::shared_ptr<const PedersenTrace> pedersen_instance_trace(const U256 &a, const U256 &b);
 // the dummy instance (a = b = 0: what nearly every block of a run holds) is traced once per process
 inline std::shared_ptr<const PedersenTrace> pedersen_instance_trace_cached(const U256 &a, const U256 &b) {
@@ -121,7 +125,7 @@ inline std::shared_ptr<const PedersenTrace> pedersen_instance_trace(const U256 &
     c->out = c->steps.back().point.x;
     Felt want;
     const Felt fa = felt_from_canonical(a), fb = felt_from_canonical(b);
-    if (ss_pedersen_hash_host(fa.data(), fb.data(), want.data()) != SS_OK || !felt_eq(want, c->out)) fail("Pedersen partial sums do not end at the hash");
+    if (ss_pedersen_hash_host(fa.data(), fb.data(), want.data()) != SS_OK || !felt_eq(want, c->out)) fail(PEDERSEN_NOT_THE_HASH);
     return c;
 }
 // a bitwise instance's cells (builtins/src/bitwise/mod.rs; trace.rs:525-667): the four values' 64 diluted parts, the four shifted
@@ -188,10 +192,23 @@ struct RcPoolPlan {
     }
 };
 
+// What the last device generation on this thread moved and where its Pedersen instances were traced (ssh_trace_last_stats): the
+// observable behind "no templates for given Pedersen instances" - the cells are the same whichever way they are made
+struct DeviceTraceStats { uint64_t bytes_uploaded = 0, pedersen_on_host = 0, pedersen_on_device = 0, templates_uploaded = 0; };
+inline DeviceTraceStats &device_trace_stats() { static thread_local DeviceTraceStats s; return s; }
+
+// the Stark field's modulus 2^251 + 17 * 2^192 + 1, little-endian limbs: a builtin input is a field element only below it
+inline bool below_modulus(const U256 &v) {
+    const uint64_t p[4] = {1, 0, 0, 0x0800000000000011ull};
+    for (int k = 3; k >= 0; --k) if (v[k] != p[k]) return v[k] < p[k];
+    return false;
+}
+
 // ---- the device backend
 class DeviceTrace {
   public:
     DeviceTrace(ss_ctx *ctx, uint64_t num_cycles, uint64_t *const *d_cols, uint32_t ncols) : ctx_(ctx), num_cycles_(num_cycles), n_(16 * num_cycles), ncols_(ncols) {
+        device_trace_stats() = DeviceTraceStats{};
         for (uint32_t c = 0; c < ncols; ++c) cols_.push_back(d_cols[c]);
         d_status_ = (uint32_t *)alloc(SS_TRACE_STATUS_WORDS * 4);
         check(ss_dev_zero(ctx_, d_status_, SS_TRACE_STATUS_WORDS * 4));
@@ -252,9 +269,33 @@ class DeviceTrace {
         const uint32_t *d_of_block = n_templates > 1 ? upload_vec(std::vector<uint32_t>(of_block)) : nullptr;
         const ss_trace_cell *d_cells = upload_vec(std::move(cells));
         const uint64_t *d_values = (const uint64_t *)upload_vec(std::move(*values));
+        device_trace_stats().templates_uploaded += n_templates;
         check(ss_trace_builtin(ctx_, cols_.data(), ncols_, d_cells, n_cells, d_values, n_templates, d_of_block, n_blocks, block_rows, addr_begin, addr_per_block,
                                d_pool_addr_));
         lap("builtin templates");
+    }
+    // the GIVEN Pedersen instances from their inputs (csrc/trace.hip trace_pedersen_*): 72 bytes each go up, the 512 curve steps are
+    // made where the cells are.  Called after builtin() has laid the dummy instance's template over all blocks.  An input that is not
+    // a field element is refused HERE, before the instances are uploaded, with the host generator's message (there the partial sums,
+    // made from the value's bits, do not end at the hash of the reduced value)
+    // host_traced: the given (not dummy) instances the section sent through pedersen_instance_trace all the same - none, as it stands
+    template <class Inst> void pedersen(const std::vector<Inst> &given, const ss_trace_pedersen_layout &layout, uint64_t block_rows, uint64_t addr_begin,
+                                        uint64_t host_traced) {
+        device_trace_stats().pedersen_on_host += host_traced;
+        if (given.empty()) return;
+        std::vector<uint64_t> recs;
+        recs.reserve(9 * given.size());
+        for (const Inst &inst : given) {
+            if (!below_modulus(inst.a) || !below_modulus(inst.b)) fail(PEDERSEN_NOT_THE_HASH);
+            recs.push_back(inst.index);
+            recs.insert(recs.end(), inst.a.begin(), inst.a.end());
+            recs.insert(recs.end(), inst.b.begin(), inst.b.end());
+        }
+        const uint64_t n_given = given.size();
+        const uint64_t *d_recs = upload_vec(std::move(recs));
+        check(ss_trace_pedersen(ctx_, cols_.data(), ncols_, n_, &layout, d_recs, n_given, n_ / block_rows, block_rows, addr_begin, d_pool_addr_, d_status_));
+        device_trace_stats().pedersen_on_device += n_given;
+        lap("pedersen instances");
     }
     // the range-check pool: plan + histogram -> the pool's cells of every cycle; then (later, in the host sections' order) the builtin
     void rc_pool(ss_trace_rc_plan &plan, const RcPoolPlan &pool, const std::vector<uint32_t> &count, int rc_col) {
@@ -303,6 +344,8 @@ class DeviceTrace {
         const uint32_t err = st[0];
         if (!err) return;
         const std::string where = std::to_string((uint32_t)~st[1]);
+        if (err & SS_TRACE_ERR_PEDERSEN_INFINITY) fail("point at infinity in a Pedersen partial sum");
+        if (err & SS_TRACE_ERR_PEDERSEN_INSTANCE) fail("a Pedersen instance the device was given is beyond the trace's slots or not a pair of field elements");
         if (err & SS_TRACE_ERR_MISSING_CELL) fail("the run reads a memory cell that memory.bin does not hold (cycle " + where + ")");
         if (err & SS_TRACE_ERR_NOT_INSTRUCTION) fail("a memory cell the run executes is not an instruction (cycle " + where + ")");
         if (err & SS_TRACE_ERR_BAD_OP1_SOURCE) fail("invalid op1 source (cycle " + where + ")");
@@ -334,6 +377,7 @@ class DeviceTrace {
     }
     void *upload(const void *src, size_t bytes) {
         void *d = alloc(bytes);
+        device_trace_stats().bytes_uploaded += bytes;
         uint64_t ticket = 0;
         check(ss_upload_async(ctx_, d, src, bytes, &ticket));
         check(ss_wait_upload(ctx_, ticket));

@@ -17,6 +17,7 @@
 #include "public_input.hpp"
 #include "trace_recursive.hpp"
 #include "trace_starknet.hpp"
+#include "device_trace.hpp"
 #include "verifier.hpp"
 
 using namespace ssh;
@@ -609,6 +610,16 @@ int ssh_prove_files(ss_ctx *ctx, int layout, const uint8_t *trace_bin, uint64_t 
         }
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+
+// what the last device generation on the calling thread (ssh_base_trace_device, ssh_prove_files_device) moved and where its Pedersen
+// instances were traced: out = {bytes uploaded by the generator, given Pedersen instances whose curve steps ran on the host, given
+// Pedersen instances traced on the device from their inputs (ss_trace_pedersen), builtin templates uploaded (all builtins)}
+int ssh_trace_last_stats(uint64_t out[4]) {
+    if (!out) { g_err = "ssh_trace_last_stats: NULL argument"; return 1; }
+    const tracedetail::DeviceTraceStats &s = tracedetail::device_trace_stats();
+    out[0] = s.bytes_uploaded; out[1] = s.pedersen_on_host; out[2] = s.pedersen_on_device; out[3] = s.templates_uploaded;
+    return 0;
 }
 
 // files -> proof with the base trace made ON the device: trace.bin / memory.bin go up as they are (25 MB where the host-made columns

@@ -495,6 +495,8 @@ struct HostBackend {
         done({COL_MEMORY});
     }
     void pedersen_done() { done({COL_PEDERSEN_X, COL_PEDERSEN_Y, COL_PEDERSEN_SUFFIX, COL_PEDERSEN_SLOPE}); }
+    static constexpr bool pedersen_on_device = false;      // every block's instance goes through builtin()
+    void pedersen_given(const std::vector<PedersenInstance> &, uint64_t, uint64_t, uint64_t) {}
 };
 
 // ---- the device backend: the same sections as uploads of plans / templates and kernel launches (device_trace.hpp, csrc/trace.hip)
@@ -518,6 +520,15 @@ struct DeviceBackend {
     }
     void memory() { dt.ordered_memory(COL_MEMORY, in.pi.public_memory, in.n / PUBLIC_MEMORY_STEP, in.pad_value, NPC_UNUSED_ADDR); }
     void pedersen_done() {}
+    // the given Pedersen instances: their inputs go up, ss_trace_pedersen makes the cells the `place` lambda of the section names
+    static constexpr bool pedersen_on_device = true;
+    void pedersen_given(const std::vector<PedersenInstance> &given, uint64_t step, uint64_t begin, uint64_t host_traced) {
+        ss_trace_pedersen_layout l{};
+        l.col_x = COL_PEDERSEN_X; l.col_y = COL_PEDERSEN_Y; l.col_suffix = COL_PEDERSEN_SUFFIX; l.col_slope = COL_PEDERSEN_SLOPE; l.row_stride = 1;
+        l.col_flag2 = COL_PEDERSEN_SLOPE; l.off_flag2 = 255; l.col_flag3 = COL_AUXILIARY; l.off_flag3 = 71;
+        l.col_pool = COL_NPC; l.off_input0 = NPC_PEDERSEN_INPUT0_ADDR; l.off_input1 = NPC_PEDERSEN_INPUT1_ADDR; l.off_output = NPC_PEDERSEN_OUTPUT_ADDR;
+        dt.pedersen(given, l, step, begin, host_traced);
+    }
 };
 
 // ExecutionTrace::new (layouts/src/starknet/trace.rs:99-987) section by section, for either backend: where a builtin's cells go is
@@ -561,7 +572,12 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
         const uint64_t step = PEDERSEN_BUILTIN_RATIO * CYCLE_HEIGHT;
         const auto given = instances_by_index(priv.pedersen, n / step, "pedersen");
         Instances<U256x2, PedersenTrace> inst;
-        inst.assign(n / step, [&](uint64_t i) { auto it = given.find((uint32_t)i); return it != given.end() ? U256x2{it->second->a, it->second->b} : U256x2{}; });
+        // the host stores every block's own instance; the device takes the dummy instance as its ONE template and makes the given ones from
+        // their inputs (pedersen_given below: they overwrite the template's cells)
+        inst.assign(n / step, [&](uint64_t i) {
+            auto it = Backend::pedersen_on_device ? given.end() : given.find((uint32_t)i);
+            return it != given.end() ? U256x2{it->second->a, it->second->b} : U256x2{};
+        });
         inst.trace_all([](const U256x2 &k) { return pedersen_instance_trace_cached(k.first, k.second); });
         be.builtin("pedersen", inst.of_block, (uint32_t)inst.keys.size(), step, pi.segments[3].begin_addr, 3, [&](auto &s, uint32_t t) {
             const PedersenTrace &c = *inst.traces[t];
@@ -579,6 +595,7 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
             s.pair(NPC_PEDERSEN_INPUT1_ADDR, 1, felt_from_canonical(inst.keys[t].second));
             s.pair(NPC_PEDERSEN_OUTPUT_ADDR, 2, c.out);
         });
+        be.pedersen_given(priv.pedersen, step, pi.segments[3].begin_addr, (uint64_t)std::count_if(inst.keys.begin(), inst.keys.end(), [](const U256x2 &k) { return k != U256x2{}; }));
         be.pedersen_done();
     }
     // ---- range-check builtin (trace.rs:388-426)

@@ -3,7 +3,14 @@
   prove      the proof alone on the resident columns (ssh_prove)
   total      ONE ssh_prove_files_device call from the files to the proof
 and, with E2E_HOST=1, the host-generated path (ssh_prove_files: generator thread + overlapped uploads) beside it.
-python tools/e2e_device.py [starknet recursive] [log_steps] ; one line per layout, flushed as it is known."""
+python tools/e2e_device.py [starknet recursive] [log_steps] [--saturate-pedersen [--packed]] [--json FILE]; one line per layout, flushed as it is known.
+--saturate-pedersen: every Pedersen slot of the statement holds a distinct seeded instance (examples.seeded_pedersen_instances: 32768 of
+them in the starknet layout at 2^20 steps) instead of the dummy one - the normal case of a real run, and the generator's worst.
+--packed: those instances handed over as packed uint64 rows (hostlib.pack_instances), converted once outside the timed calls.
+--json FILE: the raw run lists (seconds) per layout, appended as one JSON line.
+To time an EARLIER commit beside this one (profiles/pedersen_device_trace.json), copy this file and sandstorm_amd/examples.py (the seeded
+instances) onto that commit's built tree and run it there: the tool asks for hostlib.trace_last_stats only where the package has it."""
+import json
 import os
 import sys
 import time
@@ -16,7 +23,7 @@ from sandstorm_amd import backend as be, binary, examples, hostlib, public_input
 from sandstorm_amd.prover import ProofOptions                                       # noqa: E402
 
 
-def main(layouts, log_steps=20, repeats=5):
+def main(layouts, log_steps=20, repeats=5, saturate_pedersen=False, json_path=None, packed=False):
     log_n = log_steps + 4
     n = 1 << log_n
     ctx = be.Context(0)
@@ -37,6 +44,11 @@ def main(layouts, log_steps=20, repeats=5):
             air = hostlib.RecursiveHostAir(ctx, xpi, log_n, 1)
         trace_bin, memory_bin = binary.write_register_states(states), binary.write_memory(memory)
         del states, memory
+        priv = {"pedersen": examples.seeded_pedersen_instances(examples.pedersen_slots(layout, log_steps))} if saturate_pedersen else None
+        # --packed: the instances converted to the generators' uint64 rows ONCE, outside the timed calls (hostlib.pack_instances), as a
+        # caller that has parsed its private input does; without it every call converts the Python integers again
+        if priv and packed and hasattr(hostlib, "pack_instances"):
+            priv = {"pedersen": hostlib.pack_instances("pedersen", priv["pedersen"])}
         seed = public_input.public_coin_seed(xpi, coin_kind)
         dev = [ctx.alloc(32 * n) for _ in range(nb)]
         keep = []
@@ -52,7 +64,7 @@ def main(layouts, log_steps=20, repeats=5):
         for it in range(repeats + 1):
             ctx.sync()
             t0 = time.perf_counter()
-            hostlib.device_base_trace(ctx, layout, trace_bin, memory_bin, xpi, None, dev)
+            hostlib.device_base_trace(ctx, layout, trace_bin, memory_bin, xpi, priv, dev)
             ctx.sync()
             if it:
                 gen_s.append(time.perf_counter() - t0)
@@ -66,16 +78,21 @@ def main(layouts, log_steps=20, repeats=5):
         for it in range(repeats + 1):
             ctx.sync()
             t0 = time.perf_counter()
-            _, tm = hostlib.prove_files_device(ctx, layout, trace_bin, memory_bin, xpi, None, dev, air, tree_kind, n_friendly, coin_kind, seed, build_extension,
+            _, tm = hostlib.prove_files_device(ctx, layout, trace_bin, memory_bin, xpi, priv, dev, air, tree_kind, n_friendly, coin_kind, seed, build_extension,
                                                options, want_proof=False)
             ctx.sync()
             if it:
                 total_s.append(time.perf_counter() - t0)
                 inner.append(tm["trace_gen_s"])
         med = lambda v: sorted(v)[len(v) // 2]
-        print("%s 2^%d steps, %.1f MB of files: device generator %s s; proof alone %s s; files -> proof (device generator) %s s = %.3f x the proof "
+        stats = hostlib.trace_last_stats() if hasattr(hostlib, "trace_last_stats") else None
+        if json_path:
+            with open(json_path, "a") as f:
+                f.write(json.dumps({"layout": layout, "log_steps": log_steps, "pedersen_instances": len(priv["pedersen"]) if priv else 0, "packed": bool(priv) and not isinstance(priv["pedersen"], list), "gen_s": gen_s,
+                                    "prove_s": prove_s, "total_s": total_s, "trace_gen_s": inner, "last_generation": stats}) + "\n")
+        print("%s 2^%d steps%s, %.1f MB of files: device generator %s s; proof alone %s s; files -> proof (device generator) %s s = %.3f x the proof "
               "(the columns final %s s into the call)"
-              % (layout, log_steps, (len(trace_bin) + len(memory_bin)) / 1e6, " ".join("%.4f" % v for v in gen_s), " ".join("%.4f" % v for v in prove_s),
+              % (layout, log_steps, ", %d real Pedersen instances" % len(priv["pedersen"]) if priv else "", (len(trace_bin) + len(memory_bin)) / 1e6, " ".join("%.4f" % v for v in gen_s), " ".join("%.4f" % v for v in prove_s),
                  " ".join("%.4f" % v for v in total_s), med(total_s) / med(prove_s), " ".join("%.4f" % v for v in inner)), flush=True)
         for m in keep:
             m.close()
@@ -89,4 +106,5 @@ def main(layouts, log_steps=20, repeats=5):
 if __name__ == "__main__":
     names = [a for a in sys.argv[1:] if a in ("starknet", "recursive")] or ["starknet", "recursive"]
     steps = [int(a) for a in sys.argv[1:] if a.isdigit()]
-    main(names, steps[0] if steps else 20)
+    json_out = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
+    main(names, steps[0] if steps else 20, saturate_pedersen="--saturate-pedersen" in sys.argv, json_path=json_out, packed="--packed" in sys.argv)

@@ -14,7 +14,7 @@ BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_integration.py -->", "<!-- END GEN
 SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int": "c_int", "size_t": "usize", "int64_t": "i64", "void": "c_void",
            "char": "c_char", "double": "f64", "float": "f32", "ss_status": "c_int", "ss_ctx": "SsCtx", "ss_comm": "SsComm", "ss_air_program": "SsAirProgram",
            "ss_perm_operand": "SsPermOperand", "ss_gather_job": "SsGatherJob", "uint16_t": "u16", "ss_trace_layout": "SsTraceLayout",
-           "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan"}
+           "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan", "ss_trace_pedersen_layout": "SsTracePedersenLayout"}
 
 
 def prototypes(text=None):
@@ -84,6 +84,9 @@ def rust_block():
              "#[repr(C)] pub struct SsTraceRcPlan {         // ss_trace_rc_plan",
              "    pub n_slots: u64, pub n_given: u64, pub slot_rows: u64, pub addr_begin: u64, pub n_padding: u64, pub pad0: u64,",
              "    pub part_stride: u32, pub part_off: u32, pub pair_off: u32, pub rc_lo: u32, pub rc_hi: u32, pub ordered_step: u32, pub ordered_off: u32, pub unused_off: u32,", "}",
+             "#[repr(C)] pub struct SsTracePedersenLayout { // ss_trace_pedersen_layout",
+             "    pub col_x: u32, pub off_x: u32, pub col_y: u32, pub off_y: u32, pub col_suffix: u32, pub off_suffix: u32, pub col_slope: u32, pub off_slope: u32, pub row_stride: u32,",
+             "    pub col_flag2: u32, pub off_flag2: u32, pub col_flag3: u32, pub off_flag3: u32, pub col_pool: u32, pub off_input0: u32, pub off_input1: u32, pub off_output: u32,", "}",
              "#[link(name = \"sandstorm_hip\")]", "extern \"C\" {"]
     for name, ret, params in prototypes():
         args = ", ".join("%s: %s" % (p if p not in ("in", "type", "ref", "mod") else p + "_", rust_type(t)) for t, p in params)
