@@ -512,7 +512,9 @@ enum { SS_TRACE_ERR_MISSING_CELL = 1,        /* the run reads a cell memory.bin 
        SS_TRACE_ERR_TOO_MANY_GAPS = 2048,    /* more unaccessed addresses than cycles to hold them (trace.rs:594-625) */
        SS_TRACE_ERR_FILL = 4096,             /* the ordered accesses do not fill the column                          */
        SS_TRACE_ERR_PEDERSEN_INFINITY = 8192,  /* ss_trace_pedersen: a partial sum meets its constant point (see there) */
-       SS_TRACE_ERR_PEDERSEN_INSTANCE = 16384 }; /* ss_trace_pedersen: an instance's index is beyond the blocks, or an input has a bit from 252 up: skipped */
+       SS_TRACE_ERR_PEDERSEN_INSTANCE = 16384, /* ss_trace_pedersen: an instance's index is beyond the blocks, or an input has a bit from 252 up: skipped */
+       SS_TRACE_ERR_BITWISE_INSTANCE = 32768,  /* ss_trace_bitwise: the same, for a bitwise instance                    */
+       SS_TRACE_ERR_POSEIDON_INSTANCE = 65536 }; /* ss_trace_poseidon: the same, for a Poseidon instance                */
 /* memory.bin on the device: d_records = the file's bytes (n_records x (u64 address, 32-byte little-endian word), uploaded by
  * the caller) -> d_image[address] as 4 x u64; cells the file does not name are marked (all-ones: not a field element).
  * cells: entries of d_image; records beyond it are dropped (no address above n / 2 can be accessed by a valid run). */
@@ -564,6 +566,54 @@ typedef struct {
 ss_status ss_trace_pedersen(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_pedersen_layout *layout,
                             const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr,
                             uint32_t *d_status);
+/* A GIVEN bitwise instance's cells from x and y, computed on the device (builtins/src/bitwise/mod.rs:23-133; starknet
+ * trace.rs:525-667, recursive 420-588) - no template, 72 bytes per instance.  d_instances: n_given records of 9 u64 = index, x[4],
+ * y[4] (canonical little-endian limbs, both below 2^252); instance `index` owns rows [index * block_rows, (index + 1) * block_rows)
+ * of the columns (col_rows felts each; n_blocks * block_rows <= col_rows).  With SS_TRACE_BITWISE_CELLS in `what`: for value p of
+ * x, y, x & y, x ^ y, 64-bit word c and sg < 4 the diluted part (word >> sg) & 0x1111...1 at row off_part + stride_p * p + stride_c * c
+ * + stride_s * sg of col_diluted (starknet 1 + 256 p + 64 c + 16 sg, recursive 32 p + 8 c + 2 sg), and the four top segments of
+ * x & y + x ^ y shifted left by 4, 4, 4, 8 at rows off_shifted[k].  With SS_TRACE_BITWISE_PAIRS: the five memory-pool pairs
+ * (addr_begin + 5 * index + k, value) of x, y, x & y, x ^ y, x | y at rows off_pair[k] (even) of col_pool, their integer addresses in
+ * d_pool_addr[row / 2] (col_rows / 2 u32).  (The recursive layout writes the cells before the CPU's section and the pairs after it -
+ * ss_trace_cpu_cells writes the pool's rows whole -, the starknet layout both at once.)  All values Montgomery felts, bit-identical
+ * to the host generator's.  Call it AFTER ss_trace_builtin has written the dummy instance's template over all blocks: it overwrites
+ * the given ones.  The indices must be distinct.  Bit 251 of x | y does not fit the last shifted cell: the host generator refuses such
+ * an instance ("top segment does not fit") and so must the caller - host/device_trace.hpp does, before the upload.
+ * Refused with an error (nothing launched): NULL pointers (also with n_given = 0), `what` without either bit, blocks that do not fit
+ * the columns, a column >= ncols, a cell that leaves its block, an odd pool offset.  Found on the device, as a bit of d_status: an index
+ * >= n_blocks or an input with a bit from 252 up - the instance is skipped, nothing is written for it (SS_TRACE_ERR_BITWISE_INSTANCE). */
+typedef struct {
+    uint32_t col_diluted, off_part, stride_p, stride_c, stride_s;                         /* the 4 x 4 x 4 diluted parts */
+    uint32_t off_shifted[4];                                                              /* the shifted top segments (col_diluted) */
+    uint32_t col_pool, off_pair[5];                                                       /* x, y, x & y, x ^ y, x | y */
+} ss_trace_bitwise_layout;
+enum { SS_TRACE_BITWISE_CELLS = 1, SS_TRACE_BITWISE_PAIRS = 2 };
+ss_status ss_trace_bitwise(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_bitwise_layout *layout,
+                           const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t what,
+                           uint32_t *d_pool_addr, uint32_t *d_status);
+/* A GIVEN Poseidon instance's cells from its three inputs, computed on the device (builtins/src/poseidon/mod.rs:45-152; starknet
+ * trace.rs:779-888) - no template, 104 bytes per instance.  d_instances: n_given records of 13 u64 = index, in0[4], in1[4], in2[4]
+ * (canonical little-endian limbs below 2^252).  d_round_keys: the 91 rounds' keys (4 full, 83 partial, 4 full rounds), 3 Montgomery
+ * felts each, in the order the rounds take them (the caller's: the library derives no constants of its own).  Per full round r < 8 the
+ * state after the key addition at rows full_stride * r + off_full[j] and its squares at + off_full_sq[j] of col_full; per partial
+ * round k the third element after the key addition and its square at partial_stride * k + off_partial / off_partial_sq of
+ * col_partial for k < n_partial and at tail_stride * (k - tail_first) + off_tail / off_tail_sq of col_tail for k >= tail_first
+ * (starknet: rounds 0 .. 63 in the range-check column at 8 k + 3 / 7, rounds 61 .. 82 in the auxiliary column at 16 (k - 61) + 6 / 14);
+ * the six memory-pool pairs (addr_begin + 6 * index + k, value) of the three inputs and the three outputs at rows off_pair[k] (even)
+ * of col_pool, their integer addresses in d_pool_addr[row / 2].  All values Montgomery felts, bit-identical to the host generator's.
+ * Call it AFTER ss_trace_builtin has written the dummy instance's template over all blocks; the indices must be distinct.
+ * Refused with an error (nothing launched): NULL pointers (also with n_given = 0), blocks that do not fit the columns, a column
+ * >= ncols, a cell that leaves its block, n_partial or tail_first above 83, an odd pool offset.  Found on the device: an index
+ * >= n_blocks or an input with a bit from 252 up - skipped, nothing written (SS_TRACE_ERR_POSEIDON_INSTANCE). */
+typedef struct {
+    uint32_t col_full, full_stride, off_full[3], off_full_sq[3];
+    uint32_t col_partial, partial_stride, off_partial, off_partial_sq, n_partial;
+    uint32_t col_tail, tail_stride, off_tail, off_tail_sq, tail_first;
+    uint32_t col_pool, off_pair[6];
+} ss_trace_poseidon_layout;
+ss_status ss_trace_poseidon(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_poseidon_layout *layout,
+                            const uint64_t *d_round_keys, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows,
+                            uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
 /* The 16-bit range-check pool (utils.rs:357-380; starknet trace.rs:142-165, 246-292, 388-426).  The caller counts the pool's
  * values (65536 bins: the instructions' offsets, the builtin's parts) and hands over
  *   d_first[j], j <= rc_hi - rc_lo + 1: ordered values before value rc_lo + j (every value of [rc_lo, rc_hi] max(count, 1) times),

@@ -1401,7 +1401,9 @@ namespace {
 static_assert(SS_TRACE_ERR_MISSING_CELL == TRACE_ERR_MISSING_CELL && SS_TRACE_ERR_FILL == TRACE_ERR_FILL && SS_TRACE_ERR_NOT_CONTINUOUS == TRACE_ERR_NOT_CONTINUOUS &&
               SS_TRACE_ERR_PUBLIC_CELLS == TRACE_ERR_PUBLIC_CELLS && SS_TRACE_STATUS_WORDS == TRACE_ST_WORDS && SS_TRACE_NPC_OP1 == TRACE_NPC_OP1 &&
               SS_TRACE_RC_OFF_OP1 == TRACE_RC_OFF_OP1 && SS_TRACE_AUX_RES == TRACE_AUX_RES && SS_TRACE_CELL_ADDRESS == TRACE_TILE_ADDRESS &&
-              SS_TRACE_ERR_PEDERSEN_INFINITY == TRACE_ERR_PEDERSEN_INFINITY && SS_TRACE_ERR_PEDERSEN_INSTANCE == TRACE_ERR_PEDERSEN_INSTANCE,
+              SS_TRACE_ERR_PEDERSEN_INFINITY == TRACE_ERR_PEDERSEN_INFINITY && SS_TRACE_ERR_PEDERSEN_INSTANCE == TRACE_ERR_PEDERSEN_INSTANCE &&
+              SS_TRACE_ERR_BITWISE_INSTANCE == TRACE_ERR_BITWISE_INSTANCE && SS_TRACE_ERR_POSEIDON_INSTANCE == TRACE_ERR_POSEIDON_INSTANCE &&
+              SS_TRACE_BITWISE_CELLS == TRACE_BITWISE_CELLS && SS_TRACE_BITWISE_PAIRS == TRACE_BITWISE_PAIRS,
               "the header's constants are the kernels'");
 bool trace_layout_ok(const ss_trace_layout *l) {
     if (!l) return false;
@@ -1485,6 +1487,72 @@ ss_status ss_trace_pedersen(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols
     }
     ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
     HIP_TRY(launch_trace_pedersen(ctx->stream, cp, L, d_instances, n_given, n_blocks, block_rows, addr_begin, ctx->trace_ped_points, d_pool_addr, d_status));
+    return SS_OK;
+}
+namespace {
+// what ss_trace_bitwise and ss_trace_poseidon ask of their blocks and columns before anything is launched
+const char *trace_blocks_problem(const ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const void *layout, const uint64_t *d_instances,
+                                 uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, const uint32_t *d_pool_addr, const uint32_t *d_status) {
+    if (!ctx || !d_cols || !layout || !d_pool_addr || !d_status || (n_given && !d_instances)) return "NULL argument";
+    if (!ncols || ncols > (uint32_t)MAX_COLS) return "ncols out of range";
+    if (!n_blocks || !block_rows || (block_rows & 1) || col_rows > (1ull << 32) || block_rows > col_rows || n_blocks > col_rows / block_rows)
+        return "the blocks do not fit the columns";
+    if (n_given > n_blocks || n_given > 0x3ffffffull) return "more instances than blocks (or than one launch has workgroups)";
+    for (uint32_t c = 0; c < ncols; ++c) if (!d_cols[c]) return "NULL column";
+    return nullptr;
+}
+}  // namespace
+ss_status ss_trace_bitwise(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_bitwise_layout *layout,
+                           const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t what,
+                           uint32_t *d_pool_addr, uint32_t *d_status) {
+    if (const char *problem = trace_blocks_problem(ctx, d_cols, ncols, col_rows, layout, d_instances, n_given, n_blocks, block_rows, d_pool_addr, d_status))
+        return fail(SS_ERR_INVALID, "%s", problem);
+    if (!what || (what & ~(uint32_t)(SS_TRACE_BITWISE_CELLS | SS_TRACE_BITWISE_PAIRS))) return fail(SS_ERR_INVALID, "`what` names the cells, the pairs or both");
+    static_assert(sizeof(ss_trace_bitwise_layout) == sizeof(TraceBitwiseLayout), "ss_trace_bitwise_layout is TraceBitwiseLayout");
+    TraceBitwiseLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (L.col_diluted >= ncols || L.col_pool >= ncols) return fail(SS_ERR_INVALID, "a column beyond ncols");
+    if (L.off_part + 3ull * L.stride_p + 3ull * L.stride_c + 3ull * L.stride_s >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    for (uint32_t off : L.off_shifted) if (off >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    for (uint32_t off : L.off_pair)
+        if ((off & 1) || off + 1ull >= block_rows) return fail(SS_ERR_INVALID, "a memory-pool pair starts at an even row inside the block");
+    ColPtrs cp{};
+    for (uint32_t c = 0; c < ncols; ++c) cp.dst[c] = d_cols[c];
+    if (!n_given) return SS_OK;
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_bitwise(ctx->stream, cp, L, d_instances, n_given, n_blocks, block_rows, addr_begin, what, d_pool_addr, d_status));
+    return SS_OK;
+}
+ss_status ss_trace_poseidon(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_poseidon_layout *layout,
+                            const uint64_t *d_round_keys, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows,
+                            uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status) {
+    if (const char *problem = trace_blocks_problem(ctx, d_cols, ncols, col_rows, layout, d_instances, n_given, n_blocks, block_rows, d_pool_addr, d_status))
+        return fail(SS_ERR_INVALID, "%s", problem);
+    if (!d_round_keys) return fail(SS_ERR_INVALID, "NULL argument");
+    static_assert(sizeof(ss_trace_poseidon_layout) == sizeof(TracePoseidonLayout), "ss_trace_poseidon_layout is TracePoseidonLayout");
+    TracePoseidonLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (L.col_full >= ncols || L.col_partial >= ncols || L.col_tail >= ncols || L.col_pool >= ncols) return fail(SS_ERR_INVALID, "a column beyond ncols");
+    if (L.n_partial > TRACE_POSEIDON_PARTIAL_ROUNDS || L.tail_first > TRACE_POSEIDON_PARTIAL_ROUNDS)
+        return fail(SS_ERR_INVALID, "a Poseidon instance has 83 partial rounds");
+    const uint64_t full_span = (uint64_t)L.full_stride * (TRACE_POSEIDON_FULL_ROUNDS - 1);
+    for (int j = 0; j < 3; ++j)
+        if (L.off_full[j] + full_span >= block_rows || L.off_full_sq[j] + full_span >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    if (L.n_partial) {
+        const uint64_t span = (uint64_t)L.partial_stride * (L.n_partial - 1);
+        if (L.off_partial + span >= block_rows || L.off_partial_sq + span >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    }
+    if (L.tail_first < TRACE_POSEIDON_PARTIAL_ROUNDS) {
+        const uint64_t span = (uint64_t)L.tail_stride * (TRACE_POSEIDON_PARTIAL_ROUNDS - 1 - L.tail_first);
+        if (L.off_tail + span >= block_rows || L.off_tail_sq + span >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    }
+    for (uint32_t off : L.off_pair)
+        if ((off & 1) || off + 1ull >= block_rows) return fail(SS_ERR_INVALID, "a memory-pool pair starts at an even row inside the block");
+    ColPtrs cp{};
+    for (uint32_t c = 0; c < ncols; ++c) cp.dst[c] = d_cols[c];
+    if (!n_given) return SS_OK;
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_poseidon(ctx->stream, cp, L, (const Fp *)d_round_keys, d_instances, n_given, n_blocks, block_rows, addr_begin, d_pool_addr, d_status));
     return SS_OK;
 }
 namespace {

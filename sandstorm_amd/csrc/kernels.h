@@ -165,7 +165,7 @@ enum { TRACE_ST_ERRORS = 0, TRACE_ST_WHERE = 1, TRACE_ST_ZEROS = 2, TRACE_ST_ONE
 enum { TRACE_ERR_MISSING_CELL = 1, TRACE_ERR_NOT_INSTRUCTION = 2, TRACE_ERR_BAD_OP1_SOURCE = 4, TRACE_ERR_BAD_RES_LOGIC = 8, TRACE_ERR_NOT_AN_ADDRESS = 16,
        TRACE_ERR_ADDRESS_RANGE = 32, TRACE_ERR_PUBLIC_ZERO = 64, TRACE_ERR_PUBLIC_CELLS = 128, TRACE_ERR_NO_ONES = 256, TRACE_ERR_NOT_SINGLE_VALUED = 512,
        TRACE_ERR_NOT_CONTINUOUS = 1024, TRACE_ERR_TOO_MANY_GAPS = 2048, TRACE_ERR_FILL = 4096, TRACE_ERR_PEDERSEN_INFINITY = 8192,
-       TRACE_ERR_PEDERSEN_INSTANCE = 16384 };
+       TRACE_ERR_PEDERSEN_INSTANCE = 16384, TRACE_ERR_BITWISE_INSTANCE = 32768, TRACE_ERR_POSEIDON_INSTANCE = 65536 };
 hipError_t launch_trace_memory_image(hipStream_t st, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells);
 hipError_t launch_trace_cpu(hipStream_t st, const TraceLayout &L, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells,
                             const Fp &pad_value, uint64_t rc_fill, Fp *flags, Fp *npc, Fp *rc, Fp *aux, uint32_t *d_pool_addr, uint32_t *d_status);
@@ -189,6 +189,26 @@ struct TracePedersenLayout {
 static constexpr uint32_t TRACE_PEDERSEN_POINTS = 1 + 2 * 252;
 hipError_t launch_trace_pedersen(hipStream_t st, const ColPtrs &cols, const TracePedersenLayout &L, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks,
                                  uint64_t block_rows, uint64_t addr_begin, const Fp *d_points, uint32_t *d_pool_addr, uint32_t *d_status);
+// a bitwise instance's cells from x, y (= ss_trace_bitwise_layout): part sg of word c of value p (x, y, x & y, x ^ y) at row
+// off_part + stride_p * p + stride_c * c + stride_s * sg of col_diluted, the four shifted top segments, the five memory-pool pairs
+struct TraceBitwiseLayout { uint32_t col_diluted, off_part, stride_p, stride_c, stride_s, off_shifted[4], col_pool, off_pair[5]; };
+enum { TRACE_BITWISE_CELLS = 1, TRACE_BITWISE_PAIRS = 2 };       // `what`: the diluted cells, the pool pairs, or both
+hipError_t launch_trace_bitwise(hipStream_t st, const ColPtrs &cols, const TraceBitwiseLayout &L, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks,
+                                uint64_t block_rows, uint64_t addr_begin, uint32_t what, uint32_t *d_pool_addr, uint32_t *d_status);
+// a Poseidon instance's cells from its three inputs (= ss_trace_poseidon_layout): full round r's state j and its square at rows
+// full_stride * r + off_full[j] / off_full_sq[j] of col_full; partial round k < n_partial's value and square at partial_stride * k +
+// off_partial / off_partial_sq of col_partial; partial rounds tail_first .. 82 at tail_stride * (k - tail_first) + off_tail /
+// off_tail_sq of col_tail; the six memory-pool pairs (three inputs, three outputs)
+struct TracePoseidonLayout {
+    uint32_t col_full, full_stride, off_full[3], off_full_sq[3];
+    uint32_t col_partial, partial_stride, off_partial, off_partial_sq, n_partial;
+    uint32_t col_tail, tail_stride, off_tail, off_tail_sq, tail_first;
+    uint32_t col_pool, off_pair[6];
+};
+static constexpr uint32_t TRACE_POSEIDON_FULL_ROUNDS = 8, TRACE_POSEIDON_PARTIAL_ROUNDS = 83, TRACE_POSEIDON_ROUNDS = 91;
+// d_round_keys: TRACE_POSEIDON_ROUNDS x 3 Montgomery felts in the order the rounds take them (4 full, 83 partial, 4 full)
+hipError_t launch_trace_poseidon(hipStream_t st, const ColPtrs &cols, const TracePoseidonLayout &L, const Fp *d_round_keys, const uint64_t *d_instances,
+                                 uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
 hipError_t launch_trace_ordered_memory(hipStream_t st, const TraceMemoryArgs &m, uint32_t *scratch);
 
 // ---- goldilocks.hip (the 64-bit field variant)

@@ -15,6 +15,10 @@
 //                         the whole run), written into every block that holds it; address cells are affine in the block
 //   trace_pedersen_*      the GIVEN Pedersen instances from their two inputs (72 bytes each instead of a 66 KB template): the
 //                         partial sums as one chain of Jacobian additions with one inversion per instance, then one lane per row
+//   trace_bitwise_kernel  the GIVEN bitwise instances from x, y (72 bytes each): one lane per written cell - 64 diluted parts, four shifted
+//                         top segments, five memory-pool pairs
+//   trace_poseidon_kernel the GIVEN Poseidon instances from their three inputs (104 bytes each): one lane per instance walks the 91
+//                         rounds and stores every S-box input with its square (the S-box's own intermediate)
 //   trace_rc_*            the range-check builtin's parts and the pool's ordered values / padding (utils.rs:357-380):
 //                         runs located by binary search in a prefix array of the 65536-bin histogram
 //   trace_runs_kernel     the diluted pool's ordered column the same way
@@ -355,6 +359,108 @@ __global__ __launch_bounds__(PED_STEPS) void trace_pedersen_rows_kernel(ColPtrs 
     if (t == PED_STEPS - 1) ped_pool_pair(pool, pool_addr, base + L.off_output, addr0 + 2, out);
 }
 
+// ------------------------------------------------------------------------------------------------ bitwise instances from their inputs
+// A GIVEN bitwise instance (index, x, y: 9 u64) -> the cells the host generator's bitwise section writes for it (host/device_trace.hpp
+// bitwise_instance_trace; builtins/src/bitwise/mod.rs:23-133): for each of x, y, x & y, x ^ y the 4 x 4 parts (word c, bits 4 b + sg
+// moved to 4 b: already diluted), the four top segments of x & y + x ^ y shifted by 4, 4, 4, 8, and the pool pairs of x, y, x & y,
+// x ^ y, x | y.  BW_LANES lanes per instance, one per written cell or pair: an instance's stores go out side by side.  An instance whose
+// index is beyond the blocks or whose input has a bit from 252 up is skipped with TRACE_ERR_BITWISE_INSTANCE.  (Bit 251 of x | y does
+// not fit the last shifted cell: the host generator refuses such an instance and host/device_trace.hpp refuses it before the upload;
+// here the cell would get the bits that fit.)
+constexpr u32 BW_LANES = 80;                 // 64 parts, 4 shifted cells, 5 pairs, 7 idle
+constexpr u64 BW_DILUTED = 0x1111111111111111ull;
+__global__ __launch_bounds__(256) void trace_bitwise_kernel(ColPtrs cols, TraceBitwiseLayout L, const u64 *__restrict__ inst, u64 n_given, u64 n_blocks, u64 block_rows,
+                                                            u64 addr_begin, u32 what, u32 *__restrict__ pool_addr, u32 *status) {
+    const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
+    const u64 i = g / BW_LANES;
+    const u32 t = (u32)(g - i * BW_LANES);
+    if (i >= n_given) return;
+    const u64 *rec = inst + 9 * i;
+    const u64 index = rec[0];
+    if (index >= n_blocks || (rec[4] >> 60) || (rec[8] >> 60)) { if (t == 0) status_error(status, TRACE_ERR_BITWISE_INSTANCE, i); return; }
+    const u64 base = index * block_rows;
+    auto word = [&](u32 p, u32 c) {          // word c of x, y, x & y, x ^ y, x | y
+        const u64 x = rec[1 + c], y = rec[5 + c];
+        return p == 0 ? x : p == 1 ? y : p == 2 ? (x & y) : p == 3 ? (x ^ y) : (x | y);
+    };
+    if (t < 64) {
+        if (!(what & TRACE_BITWISE_CELLS)) return;
+        const u32 p = t >> 4, c = (t >> 2) & 3, sg = t & 3;
+        store_fp((Fp *)cols.dst[L.col_diluted] + base + L.off_part + L.stride_p * p + L.stride_c * c + L.stride_s * sg, fp_from_u64((word(p, c) >> sg) & BW_DILUTED));
+    } else if (t < 68) {
+        if (!(what & TRACE_BITWISE_CELLS)) return;
+        const u32 k = t - 64;
+        const u64 v = ((word(2, 3) >> k) & BW_DILUTED) + ((word(3, 3) >> k) & BW_DILUTED);
+        const u32 off = k == 0 ? L.off_shifted[0] : k == 1 ? L.off_shifted[1] : k == 2 ? L.off_shifted[2] : L.off_shifted[3];      // (selects: no lane-indexed kernel argument)
+        store_fp((Fp *)cols.dst[L.col_diluted] + base + off, fp_from_u64(v << (k == 3 ? 8 : 4)));
+    } else if (t < 73) {
+        if (!(what & TRACE_BITWISE_PAIRS)) return;
+        const u32 k = t - 68;
+        u64 w[4];
+#pragma unroll
+        for (u32 c = 0; c < 4; ++c) w[c] = word(k, c);
+        const u32 off = k == 0 ? L.off_pair[0] : k == 1 ? L.off_pair[1] : k == 2 ? L.off_pair[2] : k == 3 ? L.off_pair[3] : L.off_pair[4];
+        ped_pool_pair((Fp *)cols.dst[L.col_pool], pool_addr, base + off, addr_begin + 5 * index + k, fp_to_mont(fp_of_words(w)));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ Poseidon instances from their inputs
+// A GIVEN Poseidon instance (index, three inputs: 13 u64) -> the cells the host generator's Poseidon section writes for it
+// (host/trace_starknet.cpp poseidon_trace; builtins/src/poseidon/mod.rs:45-152): the state of each of the 8 full rounds after the key
+// addition with its squares, the third element of each of the 83 partial rounds with its square, the three outputs; the pool pairs
+// of inputs and outputs.  One lane per instance: a dependent chain of 107 S-boxes, v^3 = v^2 v with v^2 the stored cell - 214
+// products an instance, nothing computed twice.  Skipped with TRACE_ERR_POSEIDON_INSTANCE: an index beyond the blocks, an input with a
+// bit from 252 up.
+struct PoseidonState { Fp a, b, c; };
+__device__ __forceinline__ PoseidonState poseidon_mix(const PoseidonState &s) {      // (3 a + b + c, a - b + c, a + b - 2 c)
+    PoseidonState r;
+    r.a = fp_add(fp_add(fp_add(fp_add(s.a, s.a), s.a), s.b), s.c);
+    r.b = fp_add(fp_sub(s.a, s.b), s.c);
+    r.c = fp_sub(fp_add(s.a, s.b), fp_add(s.c, s.c));
+    return r;
+}
+__global__ __launch_bounds__(64) void trace_poseidon_kernel(ColPtrs cols, TracePoseidonLayout L, const Fp *__restrict__ keys, const u64 *__restrict__ inst, u64 n_given,
+                                                            u64 n_blocks, u64 block_rows, u64 addr_begin, u32 *__restrict__ pool_addr, u32 *status) {
+    const u64 g = (u64)blockIdx.x * 64 + threadIdx.x;
+    if (g >= n_given) return;
+    const u64 *rec = inst + 13 * g;
+    const u64 index = rec[0];
+    if (index >= n_blocks || (rec[4] >> 60) || (rec[8] >> 60) || (rec[12] >> 60)) { status_error(status, TRACE_ERR_POSEIDON_INSTANCE, g); return; }
+    const u64 base = index * block_rows, addr0 = addr_begin + 6 * index;
+    Fp *const full = (Fp *)cols.dst[L.col_full] + base, *const partial = (Fp *)cols.dst[L.col_partial] + base, *const tail = (Fp *)cols.dst[L.col_tail] + base;
+    Fp *const pool = (Fp *)cols.dst[L.col_pool];
+    PoseidonState s;
+    s.a = fp_to_mont(fp_of_words(rec + 1)); s.b = fp_to_mont(fp_of_words(rec + 5)); s.c = fp_to_mont(fp_of_words(rec + 9));
+    ped_pool_pair(pool, pool_addr, base + L.off_pair[0], addr0, s.a);
+    ped_pool_pair(pool, pool_addr, base + L.off_pair[1], addr0 + 1, s.b);
+    ped_pool_pair(pool, pool_addr, base + L.off_pair[2], addr0 + 2, s.c);
+    u32 r = 0;
+    auto full_round = [&](u32 rnd) {
+        s.a = fp_add(s.a, load_fp(&keys[3 * r])); s.b = fp_add(s.b, load_fp(&keys[3 * r + 1])); s.c = fp_add(s.c, load_fp(&keys[3 * r + 2]));
+        ++r;
+        Fp *const row = full + (u64)L.full_stride * rnd;
+        const Fp qa = fp_sqr(s.a), qb = fp_sqr(s.b), qc = fp_sqr(s.c);
+        store_fp(row + L.off_full[0], s.a); store_fp(row + L.off_full_sq[0], qa);
+        store_fp(row + L.off_full[1], s.b); store_fp(row + L.off_full_sq[1], qb);
+        store_fp(row + L.off_full[2], s.c); store_fp(row + L.off_full_sq[2], qc);
+        s.a = fp_mul(qa, s.a); s.b = fp_mul(qb, s.b); s.c = fp_mul(qc, s.c);
+        s = poseidon_mix(s);
+    };
+    for (u32 rnd = 0; rnd < 4; ++rnd) full_round(rnd);
+    for (u32 k = 0; k < TRACE_POSEIDON_PARTIAL_ROUNDS; ++k, ++r) {
+        s.a = fp_add(s.a, load_fp(&keys[3 * r])); s.b = fp_add(s.b, load_fp(&keys[3 * r + 1])); s.c = fp_add(s.c, load_fp(&keys[3 * r + 2]));
+        const Fp q = fp_sqr(s.c);
+        if (k < L.n_partial) { Fp *const row = partial + (u64)L.partial_stride * k; store_fp(row + L.off_partial, s.c); store_fp(row + L.off_partial_sq, q); }
+        if (k >= L.tail_first) { Fp *const row = tail + (u64)L.tail_stride * (k - L.tail_first); store_fp(row + L.off_tail, s.c); store_fp(row + L.off_tail_sq, q); }
+        s.c = fp_mul(q, s.c);
+        s = poseidon_mix(s);
+    }
+    for (u32 rnd = 4; rnd < 8; ++rnd) full_round(rnd);
+    ped_pool_pair(pool, pool_addr, base + L.off_pair[3], addr0 + 3, s.a);
+    ped_pool_pair(pool, pool_addr, base + L.off_pair[4], addr0 + 4, s.b);
+    ped_pool_pair(pool, pool_addr, base + L.off_pair[5], addr0 + 5, s.c);
+}
+
 // ------------------------------------------------------------------------------------------------ range-check builtin and pool
 // the pool's padding values in order (utils.rs:357-380 RangeCheckPool::get_ordered_values_with_padding's second half), then rc_hi
 __device__ __forceinline__ u32 rc_padding(const TraceRcPlan &p, const uint16_t *padding, u64 j) { return j < p.n_padding ? padding[j] : p.rc_hi; }
@@ -659,6 +765,20 @@ hipError_t launch_trace_pedersen(hipStream_t st, const ColPtrs &cols, const Trac
     if (!n_given) return hipSuccess;
     hipLaunchKernelGGL(trace_pedersen_sums_kernel, grid_for(n_given, 64), dim3(64), 0, st, cols, L, d_instances, n_given, n_blocks, block_rows, d_points, d_status);
     hipLaunchKernelGGL(trace_pedersen_rows_kernel, dim3((u32)n_given), dim3(PED_STEPS), 0, st, cols, L, d_instances, n_blocks, block_rows, addr_begin, d_points, d_pool_addr);
+    return hipGetLastError();
+}
+hipError_t launch_trace_bitwise(hipStream_t st, const ColPtrs &cols, const TraceBitwiseLayout &L, const u64 *d_instances, u64 n_given, u64 n_blocks, u64 block_rows,
+                                u64 addr_begin, u32 what, u32 *d_pool_addr, u32 *d_status) {
+    if (!n_given) return hipSuccess;
+    hipLaunchKernelGGL(trace_bitwise_kernel, grid_for(n_given * BW_LANES, 256), dim3(256), 0, st, cols, L, d_instances, n_given, n_blocks, block_rows, addr_begin, what,
+                       d_pool_addr, d_status);
+    return hipGetLastError();
+}
+hipError_t launch_trace_poseidon(hipStream_t st, const ColPtrs &cols, const TracePoseidonLayout &L, const Fp *d_round_keys, const u64 *d_instances, u64 n_given,
+                                 u64 n_blocks, u64 block_rows, u64 addr_begin, u32 *d_pool_addr, u32 *d_status) {
+    if (!n_given) return hipSuccess;
+    hipLaunchKernelGGL(trace_poseidon_kernel, grid_for(n_given, 64), dim3(64), 0, st, cols, L, d_round_keys, d_instances, n_given, n_blocks, block_rows, addr_begin,
+                       d_pool_addr, d_status);
     return hipGetLastError();
 }
 hipError_t launch_trace_rc_builtin(hipStream_t st, const TraceRcPlan &p, const u64 *d_given, const uint16_t *d_padding, Fp *rc, Fp *npc, u32 *d_pool_addr) {

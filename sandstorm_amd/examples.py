@@ -110,3 +110,37 @@ def seeded_pedersen_instances(slots, seed=SEED0):
     raw[:, 7] &= np.uint64((1 << 59) - 1)
     word = lambda r, k: sum(int(r[k + j]) << (64 * j) for j in range(4))
     return [(i, word(raw[i], 0), word(raw[i], 4)) for i in range(slots)]
+
+
+def bitwise_slots(layout, log_steps):
+    """bitwise builtin instances a 2^log_steps-step trace of `layout` has room for"""
+    from sandstorm_amd.layouts import recursive as rec, starknet as sk
+    return (1 << log_steps) // (sk.BITWISE_RATIO if layout == "starknet" else rec.BITWISE_RATIO)
+
+
+def poseidon_slots(log_steps):
+    """Poseidon builtin instances a 2^log_steps-step starknet trace has room for (the recursive layout has no Poseidon builtin)"""
+    from sandstorm_amd.layouts import starknet as sk
+    return (1 << log_steps) // sk.POSEIDON_RATIO
+
+
+def _seeded_values(slots, per_instance, seed):
+    """`slots` rows of `per_instance` values < 2^251 from SplitMix64, as (index, v0, v1, ...)"""
+    raw = splitmix64_stream(seed, 4 * per_instance * slots).reshape(slots, 4 * per_instance).copy()
+    raw[:, 3::4] &= np.uint64((1 << 59) - 1)
+    word = lambda r, k: sum(int(r[k + j]) << (64 * j) for j in range(4))
+    return [(i,) + tuple(word(raw[i], 4 * v) for v in range(per_instance)) for i in range(slots)]
+
+
+def seeded_bitwise_instances(slots, seed=SEED0):
+    """`slots` distinct bitwise instances (index, x, y), one per slot, as air-private-input.json's `bitwise` rows: x, y < 2^251 from
+    SplitMix64.  The example program does not touch the builtin's segment, so any inputs make a valid statement: a run whose bitwise
+    slots are all REAL instances.  Their 68 diluted cells each load the diluted pool: at most 68 * slots + 65536 ordered slots, which
+    fits the statements the suite and the tools saturate (starknet 2^17 / 2^20 steps, recursive 2^14 / 2^20 steps)"""
+    return _seeded_values(slots, 2, seed ^ 0x425457)
+
+
+def seeded_poseidon_instances(slots, seed=SEED0):
+    """`slots` distinct Poseidon instances (index, in0, in1, in2), one per slot, as air-private-input.json's `poseidon` rows: inputs
+    < 2^251 from SplitMix64 (see seeded_bitwise_instances)"""
+    return _seeded_values(slots, 3, seed ^ 0x504f53)

@@ -6,7 +6,10 @@
 //   * a section's per-instance cells are written through a Sink - HostSink stores into the host columns (the host generator),
 //     TemplateSink records them as ONE template per DISTINCT instance, which the device copies into every block that holds it;
 //   * the Pedersen builtin's GIVEN instances are the exception: the device backend uploads their inputs (72 bytes each) and
-//     ss_trace_pedersen makes their cells on the device - only the dummy instance is a template (DeviceTrace::pedersen);
+//     ss_trace_pedersen makes their cells on the device - only the dummy instance is a template (DeviceTrace::pedersen); the
+//     bitwise builtin's (x, y: 72 bytes) and the Poseidon builtin's (three inputs: 104 bytes) go the same way through ss_trace_bitwise
+//     and ss_trace_poseidon (DeviceTrace::bitwise, DeviceTrace::poseidon), and the diluted pool's histogram of the bitwise instances is
+//     counted from their inputs with integer operations (bitwise_count_inputs);
 //   * DeviceTrace uploads the raw files, plans and templates and launches the kernels in the order the host sections run
 //     (a later section overwrites an earlier one's cells, as on the host); the input's errors come back as status bits and are
 //     thrown with the host generator's messages.
@@ -130,6 +133,7 @@ inline std::shared_ptr<const PedersenTrace> pedersen_instance_trace(const U256 &
 }
 // a bitwise instance's cells (builtins/src/bitwise/mod.rs; trace.rs:525-667): the four values' 64 diluted parts, the four shifted
 // top segments of x & y + x ^ y, the five memory values; `undiluted`: the 68 diluted cells as the pool counts them
+constexpr const char *BITWISE_TOP_SEGMENT = "bitwise instance: top segment does not fit";
 struct BitwiseTrace { Felt parts[4][4][4], shifted[4], memory[5]; uint32_t undiluted[68]; };
 inline std::shared_ptr<const BitwiseTrace> bitwise_instance_trace(const U256 &x, const U256 &y) {
     auto t = std::make_shared<BitwiseTrace>();
@@ -141,7 +145,7 @@ inline std::shared_ptr<const BitwiseTrace> bitwise_instance_trace(const U256 &x,
     for (unsigned k = 0; k < 4; ++k) {
         const uint64_t v = parts[2][3][k] + parts[3][3][k];
         const unsigned sh = k == 3 ? 8 : 4;
-        if (((v << sh) >> sh) != v) fail("bitwise instance: top segment does not fit");
+        if (((v << sh) >> sh) != v) fail(BITWISE_TOP_SEGMENT);
         t->shifted[k] = felt_from_u64(v << sh);
         t->undiluted[k] = undilute(v << sh);
     }
@@ -194,7 +198,11 @@ struct RcPoolPlan {
 
 // What the last device generation on this thread moved and where its Pedersen instances were traced (ssh_trace_last_stats): the
 // observable behind "no templates for given Pedersen instances" - the cells are the same whichever way they are made
-struct DeviceTraceStats { uint64_t bytes_uploaded = 0, pedersen_on_host = 0, pedersen_on_device = 0, templates_uploaded = 0; };
+// (and its bitwise and Poseidon instances: ssh_trace_last_stats_n)
+struct DeviceTraceStats {
+    uint64_t bytes_uploaded = 0, pedersen_on_host = 0, pedersen_on_device = 0, templates_uploaded = 0;
+    uint64_t bitwise_on_host = 0, bitwise_on_device = 0, poseidon_on_host = 0, poseidon_on_device = 0;
+};
 inline DeviceTraceStats &device_trace_stats() { static thread_local DeviceTraceStats s; return s; }
 
 // the Stark field's modulus 2^251 + 17 * 2^192 + 1, little-endian limbs: a builtin input is a field element only below it
@@ -202,6 +210,69 @@ inline bool below_modulus(const U256 &v) {
     const uint64_t p[4] = {1, 0, 0, 0x0800000000000011ull};
     for (int k = 3; k >= 0; --k) if (v[k] != p[k]) return v[k] < p[k];
     return false;
+}
+
+// The given instances of a builtin that a device backend traces from their INPUTS: records of (index, n_values x 4 limbs) as the
+// ss_trace_* entry points take them, and which blocks they hold (those blocks get the dummy instance's template first).  An instance
+// with an input that is not below the modulus is left out: it keeps the template path (felt_from_canonical is specified for
+// integers < p only, so whatever the host generator makes of it is made in one place)
+struct DeviceInstances {
+    std::vector<uint64_t> recs;
+    std::vector<uint8_t> of_block;
+    uint64_t count = 0;
+    bool holds(uint64_t block) const { return !of_block.empty() && of_block[block]; }
+};
+// value_of(inst, k): input k of the instance (an U256).  The indices are checked by then (instances_by_index)
+template <class Inst, class ValueOf> DeviceInstances device_instances(bool enabled, const std::vector<Inst> &given, uint64_t slots, unsigned n_values, const ValueOf &value_of) {
+    DeviceInstances d;
+    if (!enabled || given.empty()) return d;
+    d.of_block.assign(slots, 0);
+    d.recs.reserve((1 + 4 * n_values) * given.size());
+    for (const Inst &inst : given) {
+        bool field = true;
+        for (unsigned k = 0; k < n_values; ++k) field = field && below_modulus(value_of(inst, k));
+        if (!field) continue;
+        d.of_block[inst.index] = 1;
+        d.recs.push_back(inst.index);
+        for (unsigned k = 0; k < n_values; ++k) { const U256 &v = value_of(inst, k); d.recs.insert(d.recs.end(), v.begin(), v.end()); }
+        ++d.count;
+    }
+    return d;
+}
+// bits 4 i of v -> bits i (what undilute() makes of a value in diluted form), by shifts and masks
+inline uint32_t compress_diluted(uint64_t v) {
+    v &= 0x1111111111111111ull;
+    v = (v | (v >> 3)) & 0x0303030303030303ull;
+    v = (v | (v >> 6)) & 0x000f000f000f000full;
+    v = (v | (v >> 12)) & 0x000000ff000000ffull;
+    v = (v | (v >> 24)) & 0xffffull;
+    return (uint32_t)v;
+}
+// the diluted pool's histogram of bitwise instances (records of index, x, y) from their inputs: the 68 values undilute() gives for the
+// cells of bitwise_instance_trace - integer operations only, no Felt, on all threads - added to `count`; with that function's own
+// refusal of an instance whose top segment does not fit its shifted cell
+inline void bitwise_count_inputs(const std::vector<uint64_t> &recs, std::vector<uint32_t> &count) {
+    const uint64_t n_inst = recs.size() / 9;
+    if (!n_inst) return;
+    bool too_wide = false;
+    std::vector<std::vector<uint32_t>> count_of((size_t)omp_get_max_threads());
+#pragma omp parallel for schedule(static) reduction(|| : too_wide)
+    for (uint64_t i = 0; i < n_inst; ++i) {
+        std::vector<uint32_t> &mine = count_of[(size_t)omp_get_thread_num()];
+        if (mine.empty()) mine.assign(1u << DILUTED_N_BITS, 0);
+        const uint64_t *x = &recs[9 * i + 1], *y = x + 4;
+        if ((x[3] | y[3]) >> 59) { too_wide = true; continue; }      // bits 252 .. 255 leave a shift by 4, bits 251 and 255 the shift by 8
+        for (unsigned c = 0; c < 4; ++c) {
+            const uint64_t w[4] = {x[c], y[c], x[c] & y[c], x[c] ^ y[c]};
+            for (unsigned p = 0; p < 4; ++p) for (unsigned sg = 0; sg < 4; ++sg) ++mine[compress_diluted(w[p] >> sg)];
+        }
+        for (unsigned k = 0; k < 4; ++k) {
+            const uint64_t m = 0x1111111111111111ull, v = (((x[3] & y[3]) >> k) & m) + (((x[3] ^ y[3]) >> k) & m);
+            ++mine[compress_diluted(v << (k == 3 ? 8 : 4))];
+        }
+    }
+    if (too_wide) fail(BITWISE_TOP_SEGMENT);
+    for (auto &part : count_of) for (size_t v = 0; v < part.size(); ++v) count[v] += part[v];
 }
 
 // ---- the device backend
@@ -297,6 +368,28 @@ class DeviceTrace {
         device_trace_stats().pedersen_on_device += n_given;
         lap("pedersen instances");
     }
+    // the GIVEN bitwise instances from x, y (csrc/trace.hip trace_bitwise_kernel).  Called after builtin() has laid the dummy
+    // instance's template over all blocks; the recursive layout calls it twice - the diluted cells before the CPU's section, the pool
+    // pairs after it - and the records go up once.  host_traced: the given (not dummy) instances that went through a template
+    void bitwise(DeviceInstances &dev, const ss_trace_bitwise_layout &layout, uint64_t block_rows, uint64_t addr_begin, uint32_t what, uint64_t host_traced) {
+        if (what & SS_TRACE_BITWISE_CELLS) device_trace_stats().bitwise_on_host += host_traced;
+        if (!dev.count) return;
+        if (!d_bitwise_recs_) d_bitwise_recs_ = upload_vec(std::move(dev.recs));
+        check(ss_trace_bitwise(ctx_, cols_.data(), ncols_, n_, &layout, d_bitwise_recs_, dev.count, n_ / block_rows, block_rows, addr_begin, what, d_pool_addr_, d_status_));
+        if (what & SS_TRACE_BITWISE_CELLS) device_trace_stats().bitwise_on_device += dev.count;
+        lap("bitwise instances");
+    }
+    // the GIVEN Poseidon instances from their three inputs (csrc/trace.hip trace_poseidon_kernel); round_keys: the host's
+    // poseidon_round_keys() (91 x 3 Montgomery felts, uploaded once per generation - the device derives no constants)
+    void poseidon(DeviceInstances &dev, const ss_trace_poseidon_layout &layout, const Felt *round_keys, uint64_t block_rows, uint64_t addr_begin, uint64_t host_traced) {
+        device_trace_stats().poseidon_on_host += host_traced;
+        if (!dev.count) return;
+        const uint64_t *d_keys = (const uint64_t *)upload(round_keys, 91 * 3 * sizeof(Felt));
+        const uint64_t *d_recs = upload_vec(std::move(dev.recs));
+        check(ss_trace_poseidon(ctx_, cols_.data(), ncols_, n_, &layout, d_keys, d_recs, dev.count, n_ / block_rows, block_rows, addr_begin, d_pool_addr_, d_status_));
+        device_trace_stats().poseidon_on_device += dev.count;
+        lap("poseidon instances");
+    }
     // the range-check pool: plan + histogram -> the pool's cells of every cycle; then (later, in the host sections' order) the builtin
     void rc_pool(ss_trace_rc_plan &plan, const RcPoolPlan &pool, const std::vector<uint32_t> &count, int rc_col) {
         plan.rc_lo = pool.lo; plan.rc_hi = pool.hi; plan.n_padding = pool.padding.size(); plan.pad0 = pool.pad0;
@@ -346,6 +439,8 @@ class DeviceTrace {
         const std::string where = std::to_string((uint32_t)~st[1]);
         if (err & SS_TRACE_ERR_PEDERSEN_INFINITY) fail("point at infinity in a Pedersen partial sum");
         if (err & SS_TRACE_ERR_PEDERSEN_INSTANCE) fail("a Pedersen instance the device was given is beyond the trace's slots or not a pair of field elements");
+        if (err & SS_TRACE_ERR_BITWISE_INSTANCE) fail("a bitwise instance the device was given is beyond the trace's slots or not a pair of field elements");
+        if (err & SS_TRACE_ERR_POSEIDON_INSTANCE) fail("a Poseidon instance the device was given is beyond the trace's slots or not three field elements");
         if (err & SS_TRACE_ERR_MISSING_CELL) fail("the run reads a memory cell that memory.bin does not hold (cycle " + where + ")");
         if (err & SS_TRACE_ERR_NOT_INSTRUCTION) fail("a memory cell the run executes is not an instruction (cycle " + where + ")");
         if (err & SS_TRACE_ERR_BAD_OP1_SOURCE) fail("invalid op1 source (cycle " + where + ")");
@@ -397,6 +492,7 @@ class DeviceTrace {
     const bool timing_ = getenv("SSH_TRACE_TIMING") != nullptr;
     std::chrono::steady_clock::time_point t_last_ = std::chrono::steady_clock::now();
     const uint32_t *d_rc_first_ = nullptr;
+    const uint64_t *d_bitwise_recs_ = nullptr;
     const uint16_t *d_rc_padding_ = nullptr;
 };
 

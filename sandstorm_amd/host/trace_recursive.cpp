@@ -261,6 +261,8 @@ struct HostBackend {
     }
     static constexpr bool pedersen_on_device = false;      // every block's instance goes through builtin()
     void pedersen_given(const std::vector<PedersenInstance> &, uint64_t, uint64_t, uint64_t) {}
+    static constexpr bool bitwise_on_device = false;
+    void bitwise_given(DeviceInstances &, uint64_t, uint64_t, uint32_t, uint64_t) {}
 };
 
 // ---- the device backend: the same sections as uploads of plans / templates and kernel launches (device_trace.hpp, csrc/trace.hip)
@@ -294,6 +296,16 @@ struct DeviceBackend {
         l.col_pool = COL_NPC; l.off_input0 = NPC_PEDERSEN_INPUT0_ADDR; l.off_input1 = NPC_PEDERSEN_INPUT1_ADDR; l.off_output = NPC_PEDERSEN_OUTPUT_ADDR;
         dt.pedersen(given, l, step, begin, host_traced);
     }
+    // the given bitwise instances the same way (ss_trace_bitwise): the diluted cells with the section, the pool pairs after the CPU's
+    static constexpr bool bitwise_on_device = true;
+    void bitwise_given(DeviceInstances &dev, uint64_t step, uint64_t begin, uint32_t what, uint64_t host_traced) {
+        ss_trace_bitwise_layout l{};
+        l.col_diluted = COL_DILUTED_UNORDERED; l.off_part = 0; l.stride_p = 32; l.stride_c = 8; l.stride_s = 2;
+        const uint32_t shifted_cells[4] = {1, 65, 33, 97};
+        for (int k = 0; k < 4; ++k) { l.off_shifted[k] = shifted_cells[k]; l.off_pair[k] = NPC_BITWISE_POOL_ADDR + k * (uint32_t)(step / 4); }
+        l.col_pool = COL_NPC; l.off_pair[4] = NPC_BITWISE_X_OR_Y_ADDR;
+        dt.bitwise(dev, l, step, begin, what, host_traced);
+    }
 };
 
 // ExecutionTrace::new (layouts/src/recursive/trace.rs:89-688) section by section, for either backend: where a builtin's cells go is said
@@ -308,8 +320,14 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
     // memory cells wait for the CPU section, which writes the memory pool's rows whole (below)
     const uint64_t bw_step = BITWISE_RATIO * CYCLE_HEIGHT;
     const auto bw_given = instances_by_index(priv.bitwise, n / bw_step, "bitwise");
+    // the device makes the given instances' cells from x, y (bitwise_given below) and takes the dummy instance as its one template
+    DeviceInstances bw_dev = device_instances(Backend::bitwise_on_device, priv.bitwise, n / bw_step, 2, [](const BitwiseInstance &b, unsigned k) -> const U256 & { return k ? b.y : b.x; });
     Instances<U256x2, BitwiseTrace> bitwise;
-    bitwise.assign(n / bw_step, [&](uint64_t i) { auto it = bw_given.find((uint32_t)i); return it != bw_given.end() ? U256x2{it->second->x, it->second->y} : U256x2{}; });
+    bitwise.assign(n / bw_step, [&](uint64_t i) {
+        auto it = bw_dev.holds(i) ? bw_given.end() : bw_given.find((uint32_t)i);
+        return it != bw_given.end() ? U256x2{it->second->x, it->second->y} : U256x2{};
+    });
+    const uint64_t bw_host_traced = (uint64_t)std::count_if(bitwise.keys.begin(), bitwise.keys.end(), [](const U256x2 &k) { return k != U256x2{}; });
     bitwise.trace_all([](const U256x2 &k) { return bitwise_instance_trace(k.first, k.second); });
     {
         const uint64_t shifted_cells[4] = {1, 65, 33, 97};
@@ -318,10 +336,13 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
             for (int k = 0; k < 4; ++k) s.cell(COL_DILUTED_UNORDERED, shifted_cells[k], t.shifted[k]);
             for (int p = 0; p < 4; ++p) for (int c = 0; c < 4; ++c) for (int sg = 0; sg < 4; ++sg) s.cell(COL_DILUTED_UNORDERED, 32 * p + 8 * c + 2 * sg, t.parts[p][c][sg]);
         });
-        // the diluted pool: every instance's 68 diluted cells counted (by template: nearly every block holds the dummy instance)
+        // the diluted pool: every instance's 68 diluted cells counted (by template: nearly every block holds the dummy instance; the
+        // device's instances from their inputs - with the host's refusal of a top segment that does not fit, before anything goes up)
         std::vector<uint32_t> dil_count(1u << DILUTED_N_BITS, 0), blocks_of(bitwise.keys.size(), 0);
-        for (uint32_t t : bitwise.of_block) ++blocks_of[t];
+        for (uint64_t i = 0; i < bitwise.of_block.size(); ++i) if (!bw_dev.holds(i)) ++blocks_of[bitwise.of_block[i]];
         for (size_t t = 0; t < bitwise.keys.size(); ++t) for (uint32_t v : bitwise.traces[t]->undiluted) dil_count[v] += blocks_of[t];
+        bitwise_count_inputs(bw_dev.recs, dil_count);
+        be.bitwise_given(bw_dev, bw_step, bw_seg.begin_addr, SS_TRACE_BITWISE_CELLS, bw_host_traced);
         DilutedPlan dp;
         dp.from_counts(dil_count, n);
         dp.first[0] = 0;                // the rows before the first value are zeros, and so is the first value's image: one run from row 0
@@ -371,6 +392,7 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
         for (int k = 0; k < 4; ++k) s.pair(NPC_BITWISE_POOL_ADDR + k * (bw_step / 4), k, t.memory[k]);
         s.pair(NPC_BITWISE_X_OR_Y_ADDR, 4, t.memory[4]);
     });
+    be.bitwise_given(bw_dev, bw_step, bw_seg.begin_addr, SS_TRACE_BITWISE_PAIRS, bw_host_traced);
     // ---- Pedersen builtin (trace.rs:300-400; builtins/src/pedersen/mod.rs:81-163)
     {
         const uint64_t step = PEDERSEN_BUILTIN_RATIO * CYCLE_HEIGHT;

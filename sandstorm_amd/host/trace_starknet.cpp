@@ -497,6 +497,9 @@ struct HostBackend {
     void pedersen_done() { done({COL_PEDERSEN_X, COL_PEDERSEN_Y, COL_PEDERSEN_SUFFIX, COL_PEDERSEN_SLOPE}); }
     static constexpr bool pedersen_on_device = false;      // every block's instance goes through builtin()
     void pedersen_given(const std::vector<PedersenInstance> &, uint64_t, uint64_t, uint64_t) {}
+    static constexpr bool bitwise_on_device = false, poseidon_on_device = false;
+    void bitwise_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
+    void poseidon_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
 };
 
 // ---- the device backend: the same sections as uploads of plans / templates and kernel launches (device_trace.hpp, csrc/trace.hip)
@@ -528,6 +531,27 @@ struct DeviceBackend {
         l.col_flag2 = COL_PEDERSEN_SLOPE; l.off_flag2 = 255; l.col_flag3 = COL_AUXILIARY; l.off_flag3 = 71;
         l.col_pool = COL_NPC; l.off_input0 = NPC_PEDERSEN_INPUT0_ADDR; l.off_input1 = NPC_PEDERSEN_INPUT1_ADDR; l.off_output = NPC_PEDERSEN_OUTPUT_ADDR;
         dt.pedersen(given, l, step, begin, host_traced);
+    }
+    // the given bitwise and Poseidon instances the same way: ss_trace_bitwise / ss_trace_poseidon make the cells their sections' `place`
+    // lambdas name
+    static constexpr bool bitwise_on_device = true, poseidon_on_device = true;
+    void bitwise_given(DeviceInstances &dev, uint64_t step, uint64_t begin, uint64_t host_traced) {
+        ss_trace_bitwise_layout l{};
+        l.col_diluted = COL_RANGE_CHECK; l.off_part = 1; l.stride_p = 256; l.stride_c = 64; l.stride_s = 16;
+        for (int k = 0; k < 4; ++k) { l.off_shifted[k] = (uint32_t)BITWISE_SHIFTED_CELLS[k]; l.off_pair[k] = NPC_BITWISE_POOL_ADDR + 256 * k; }
+        l.col_pool = COL_NPC; l.off_pair[4] = NPC_BITWISE_X_OR_Y_ADDR;
+        dt.bitwise(dev, l, step, begin, SS_TRACE_BITWISE_CELLS | SS_TRACE_BITWISE_PAIRS, host_traced);
+    }
+    void poseidon_given(DeviceInstances &dev, uint64_t step, uint64_t begin, uint64_t host_traced) {
+        ss_trace_poseidon_layout l{};
+        const uint32_t full[3][2] = {{53, 29}, {13, 61}, {45, 3}};
+        l.col_full = COL_AUXILIARY; l.full_stride = 64;
+        for (int j = 0; j < 3; ++j) { l.off_full[j] = full[j][0]; l.off_full_sq[j] = full[j][1]; }
+        l.col_partial = COL_RANGE_CHECK; l.partial_stride = 8; l.off_partial = 3; l.off_partial_sq = 7; l.n_partial = 64;
+        l.col_tail = COL_AUXILIARY; l.tail_stride = 16; l.off_tail = 6; l.off_tail_sq = 14; l.tail_first = 61;
+        l.col_pool = COL_NPC;
+        for (int k = 0; k < 6; ++k) l.off_pair[k] = (uint32_t)NPC_POSEIDON_ADDRS[k];
+        dt.poseidon(dev, l, poseidon_round_keys().data()->data(), step, begin, host_traced);
     }
 };
 
@@ -646,8 +670,13 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
     {
         const uint64_t step = BITWISE_RATIO * CYCLE_HEIGHT;
         const auto given = instances_by_index(priv.bitwise, n / step, "bitwise");
+        // the device makes the given instances' cells from x, y (bitwise_given below) and takes the dummy instance as its one template
+        DeviceInstances dev = device_instances(Backend::bitwise_on_device, priv.bitwise, n / step, 2, [](const BitwiseInstance &b, unsigned k) -> const U256 & { return k ? b.y : b.x; });
         Instances<U256x2, BitwiseTrace> inst;
-        inst.assign(n / step, [&](uint64_t i) { auto it = given.find((uint32_t)i); return it != given.end() ? U256x2{it->second->x, it->second->y} : U256x2{}; });
+        inst.assign(n / step, [&](uint64_t i) {
+            auto it = dev.holds(i) ? given.end() : given.find((uint32_t)i);
+            return it != given.end() ? U256x2{it->second->x, it->second->y} : U256x2{};
+        });
         inst.trace_all([](const U256x2 &k) { return bitwise_instance_trace(k.first, k.second); });
         be.builtin("bitwise", inst.of_block, (uint32_t)inst.keys.size(), step, pi.segments[6].begin_addr, 5, [&](auto &s, uint32_t ti) {
             const BitwiseTrace &t = *inst.traces[ti];
@@ -656,10 +685,13 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
             for (int k = 0; k < 4; ++k) s.pair(NPC_BITWISE_POOL_ADDR + 256 * k, k, t.memory[k]);
             s.pair(NPC_BITWISE_X_OR_Y_ADDR, 4, t.memory[4]);
         });
-        // the diluted pool: every instance's 68 diluted cells counted (by template: nearly every block holds the dummy instance)
+        // the diluted pool: every instance's 68 diluted cells counted (by template: nearly every block holds the dummy instance; the
+        // device's instances from their inputs - with the host's refusal of a top segment that does not fit, before anything goes up)
         std::vector<uint32_t> dil_count(1u << DILUTED_N_BITS, 0), blocks_of(inst.keys.size(), 0);
-        for (uint32_t t : inst.of_block) ++blocks_of[t];
+        for (uint64_t i = 0; i < inst.of_block.size(); ++i) if (!dev.holds(i)) ++blocks_of[inst.of_block[i]];
         for (size_t t = 0; t < inst.keys.size(); ++t) for (uint32_t v : inst.traces[t]->undiluted) dil_count[v] += blocks_of[t];
+        bitwise_count_inputs(dev.recs, dil_count);
+        be.bitwise_given(dev, step, pi.segments[6].begin_addr, (uint64_t)std::count_if(inst.keys.begin(), inst.keys.end(), [](const U256x2 &k) { return k != U256x2{}; }));
         const uint64_t slots = n / DILUTED_CHECK_STEP;
         DilutedPlan dp;
         dp.from_counts(dil_count, slots);
@@ -727,9 +759,10 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
         const uint64_t step = POSEIDON_RATIO * CYCLE_HEIGHT;
         const uint64_t FULL[3][2] = {{53, 29}, {13, 61}, {45, 3}};
         const auto given = instances_by_index(priv.poseidon, n / step, "poseidon");
+        DeviceInstances dev = device_instances(Backend::poseidon_on_device, priv.poseidon, n / step, 3, [](const PoseidonInstance &q, unsigned k) -> const U256 & { return q.input[k]; });
         Instances<U256x3, PoseidonTrace> inst;
         inst.assign(n / step, [&](uint64_t i) {
-            auto it = given.find((uint32_t)i);
+            auto it = dev.holds(i) ? given.end() : given.find((uint32_t)i);
             return it != given.end() ? U256x3{it->second->input[0], it->second->input[1], it->second->input[2]} : U256x3{};
         });
         inst.trace_all([](const U256x3 &k) {
@@ -745,6 +778,7 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
             for (uint64_t k = 0; k + 61 < t.partial.size(); ++k) { s.cell(COL_AUXILIARY, 16 * k + 6, t.partial[61 + k]); s.cell(COL_AUXILIARY, 16 * k + 14, t.partial_sq[61 + k]); }
             for (int k = 0; k < 3; ++k) { s.pair(NPC_POSEIDON_ADDRS[k], k, input[k]); s.pair(NPC_POSEIDON_ADDRS[3 + k], 3 + k, t.out[k]); }
         });
+        be.poseidon_given(dev, step, pi.segments[8].begin_addr, (uint64_t)std::count_if(inst.keys.begin(), inst.keys.end(), [](const U256x3 &k) { return k != U256x3{}; }));
     }
     // ---- gap fillers (trace.rs:890-925), sorted memory (get_ordered_memory_accesses, utils.rs:112-152)
     be.memory();

@@ -14,7 +14,8 @@ BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_integration.py -->", "<!-- END GEN
 SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int": "c_int", "size_t": "usize", "int64_t": "i64", "void": "c_void",
            "char": "c_char", "double": "f64", "float": "f32", "ss_status": "c_int", "ss_ctx": "SsCtx", "ss_comm": "SsComm", "ss_air_program": "SsAirProgram",
            "ss_perm_operand": "SsPermOperand", "ss_gather_job": "SsGatherJob", "uint16_t": "u16", "ss_trace_layout": "SsTraceLayout",
-           "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan", "ss_trace_pedersen_layout": "SsTracePedersenLayout"}
+           "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan", "ss_trace_pedersen_layout": "SsTracePedersenLayout",
+           "ss_trace_bitwise_layout": "SsTraceBitwiseLayout", "ss_trace_poseidon_layout": "SsTracePoseidonLayout"}
 
 
 def prototypes(text=None):
@@ -87,6 +88,12 @@ def rust_block():
              "#[repr(C)] pub struct SsTracePedersenLayout { // ss_trace_pedersen_layout",
              "    pub col_x: u32, pub off_x: u32, pub col_y: u32, pub off_y: u32, pub col_suffix: u32, pub off_suffix: u32, pub col_slope: u32, pub off_slope: u32, pub row_stride: u32,",
              "    pub col_flag2: u32, pub off_flag2: u32, pub col_flag3: u32, pub off_flag3: u32, pub col_pool: u32, pub off_input0: u32, pub off_input1: u32, pub off_output: u32,", "}",
+             "#[repr(C)] pub struct SsTraceBitwiseLayout {  // ss_trace_bitwise_layout",
+             "    pub col_diluted: u32, pub off_part: u32, pub stride_p: u32, pub stride_c: u32, pub stride_s: u32, pub off_shifted: [u32; 4], pub col_pool: u32, pub off_pair: [u32; 5],", "}",
+             "#[repr(C)] pub struct SsTracePoseidonLayout { // ss_trace_poseidon_layout",
+             "    pub col_full: u32, pub full_stride: u32, pub off_full: [u32; 3], pub off_full_sq: [u32; 3],",
+             "    pub col_partial: u32, pub partial_stride: u32, pub off_partial: u32, pub off_partial_sq: u32, pub n_partial: u32,",
+             "    pub col_tail: u32, pub tail_stride: u32, pub off_tail: u32, pub off_tail_sq: u32, pub tail_first: u32, pub col_pool: u32, pub off_pair: [u32; 6],", "}",
              "#[link(name = \"sandstorm_hip\")]", "extern \"C\" {"]
     for name, ret, params in prototypes():
         args = ", ".join("%s: %s" % (p if p not in ("in", "type", "ref", "mod") else p + "_", rust_type(t)) for t, p in params)
