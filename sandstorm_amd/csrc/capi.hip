@@ -1082,8 +1082,10 @@ ss_status ss_merkle_build_ex(ss_ctx *ctx, int tree_kind, uint32_t n_friendly_lay
     if (leaf_order != SS_ORDER_NATURAL && leaf_order != SS_ORDER_BITREV) return fail(SS_ERR_INVALID, "bad leaf order %d", leaf_order);
     uint32_t log_n = 0;
     while ((1ull << log_n) < n) ++log_n;
-    if (leaf_kind == SS_LEAF_FELT && leaf_order == SS_ORDER_BITREV) {
-        // single-column matrix committed in bit-reversed order: its permuted image is the leaf array
+    // single-column matrix committed in bit-reversed order: its permuted image is the leaf array.  The hash trees read the column
+    // where it lies and scatter what they write (launch_hash_felt_pairs); the Pedersen leaves take a copy
+    const bool leaves_bitrev = leaf_kind == SS_LEAF_FELT && leaf_order == SS_ORDER_BITREV && tree_kind != SS_TREE_FRIENDLY;
+    if (leaf_kind == SS_LEAF_FELT && leaf_order == SS_ORDER_BITREV && !leaves_bitrev) {
         ss_status pst = ctx->ensure_scratch2(n * sizeof(Fp));
         if (pst != SS_OK) return pst;
         HIP_TRY(launch_bitrev_copy(ctx->stream, (const Fp *)d_leaves, log_n, (Fp *)ctx->scratch2));
@@ -1103,7 +1105,8 @@ ss_status ss_merkle_build_ex(ss_ctx *ctx, int tree_kind, uint32_t n_friendly_lay
     if (d_tags) HIP_TRY(hipMemsetAsync(d_tags, 0, 2 * n, s));
     // leaf slots
     if (leaf_kind == SS_LEAF_FELT) {
-        HIP_TRY(launch_felts_to_be(s, (const Fp *)d_leaves, n, d_nodes + 32 * n));
+        // (the hash trees' leaf level writes them as it reads the felts: launch_hash_felt_pairs below)
+        if (tree_kind == SS_TREE_FRIENDLY) HIP_TRY(launch_felts_to_be(s, (const Fp *)d_leaves, n, d_nodes + 32 * n));
     } else {
         HIP_TRY(hipMemcpyAsync(d_nodes + 32 * n, d_leaves, 32 * n, hipMemcpyDeviceToDevice, s));
         if (d_tags && tree_kind == SS_TREE_FRIENDLY) HIP_TRY(hipMemsetAsync(d_tags + n, 1, n, s));
@@ -1126,7 +1129,7 @@ ss_status ss_merkle_build_ex(ss_ctx *ctx, int tree_kind, uint32_t n_friendly_lay
                 if (d_tags) HIP_TRY(hipMemsetAsync(d_tags + count, 1, count, s));
             }
         } else if (leaf_level && leaf_kind == SS_LEAF_FELT) {
-            HIP_TRY(launch_hash_felt_pairs(s, hk, (const Fp *)d_leaves, count, out));
+            HIP_TRY(launch_hash_felt_pairs(s, hk, (const Fp *)d_leaves, count, leaves_bitrev, out, d_nodes + 32 * n));
         } else {
             HIP_TRY(launch_hash_pairs(s, hk, in, count, out));
         }

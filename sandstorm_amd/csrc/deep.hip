@@ -24,7 +24,9 @@
 //    re-expanded by two NTTs — half the pointwise work for blowup 2.  Products are
 //    accumulated in the lazy 9 x 28-bit form with one weak reduction per 12 terms.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdlib>
+#include <mutex>
 #include "fp252.h"
 #include "fl252.h"
 #include "inv252.h"
@@ -241,26 +243,40 @@ hipError_t launch_ood_fold(hipStream_t st, const OodFoldArray *d_arrays, uint32_
 // kernel ran at the memory system's pace, not the multiplier's), and the lane's points are a geometric sequence of ratio w^m.
 // r280 != 0: the table is written in R280 form (fl252.h: entries times 2^24, for fl_mul_r280 consumers);
 // the factor rides on the running inverse, so it costs one multiplication per chunk.
+// A zero difference, x_i == z, zeroes the product of its chunk: the launch then writes *flag = ticket (flag null: nothing), and the
+// launcher's second launch, ZERO_AWARE, which does nothing unless *flag == ticket, makes the table again with every zero difference
+// replaced by 1 in the products and its entry written as 0 - the table is 0 exactly where x_i == z.  (A zero test per difference:
+// kept out of the launch that every table takes.)
+template <bool ZERO_AWARE>
 __global__ __launch_bounds__(128) void batch_inverse_kernel(Fp *__restrict__ D, uint64_t nchunks, uint32_t log_chunk,
-                                                            Fp offset, Fp w, Fp step, Fp step_inv, Fp z, int r280) {
+                                                            Fp offset, Fp w, Fp step, Fp step_inv, Fp z, int r280,
+                                                            uint32_t *__restrict__ flag, uint32_t ticket) {
     const uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (c >= nchunks) return;
+    if (ZERO_AWARE && *flag != ticket) return;
     const uint64_t CH = 1ull << log_chunk;
     const Fl sl = fl_from_fp(step), sil = fl_from_fp(step_inv), zl = fl_from_fp(z);
     Fl x = fl_from_fp(fp_mul(offset, fp_pow_u64(w, c)));
     Fl run = fl_one();
     for (uint64_t k = 0; k < CH; ++k) {
         dstore(D + c + k * nchunks, fl_pack(run));   // prefix product of the chunk's d_0 .. d_{k-1} (weakly reduced image)
-        run = fl_mul(fl_sub_c<2, 1>(x, zl), run);
+        Fl d = fl_sub_c<2, 1>(x, zl);
+        if (ZERO_AWARE) { d = fl_weak_reduce(d); if (fn_is_zero(d)) d = fl_one(); }
+        run = fl_mul(d, run);
         x = fl_mul(x, sl);
     }
-    Fl inv = fl_from_fp(fp_inv_safegcd(fl_to_fp(fl_weak_reduce(run))));   // 1 / (d_0 ... d_{CH-1}); 0 stays 0 if some x_i == z
+    const Fp inv_fp = fp_inv_safegcd(fl_to_fp(fl_weak_reduce(run)));      // 1 / (d_0 ... d_{CH-1}); 0 stays 0 if some x_i == z
+    if (!ZERO_AWARE && flag && fp_is_zero(inv_fp)) *flag = ticket;
+    Fl inv = fl_from_fp(inv_fp);
     if (r280) { Fp two24 = fp_zero(); two24.v[0] = 1u << 24; inv = fl_mul(inv, fl_from_fp(fp_to_mont(two24))); }
     for (uint64_t k = CH; k-- > 0;) {
         x = fl_mul(x, sil);                          // the chunk's point k
         const Fl pre = fl_from_fp(dload(D + c + k * nchunks));
-        dstore(D + c + k * nchunks, fl_to_fp(fl_mul(inv, pre)));
-        inv = fl_mul(fl_sub_c<2, 1>(x, zl), inv);
+        Fl d = fl_sub_c<2, 1>(x, zl);
+        bool zero = false;
+        if (ZERO_AWARE) { d = fl_weak_reduce(d); zero = fn_is_zero(d); if (zero) d = fl_one(); }
+        dstore(D + c + k * nchunks, zero ? fp_zero() : fl_to_fp(fl_mul(inv, pre)));
+        inv = fl_mul(d, inv);
     }
 }
 
@@ -274,13 +290,127 @@ static uint32_t batch_inverse_log_chunk(uint32_t log_N) {
     return log_chunk;
 }
 
+static hipError_t launch_batch_inverse_strided(hipStream_t st, Fp *D, uint64_t nchunks, uint32_t log_chunk, const Fp &x0, const Fp &w, const Fp &w_inv,
+                                               const Fp &z, bool r280, uint32_t *flag, uint32_t ticket, bool zero_aware) {
+    const dim3 grid((uint32_t)((nchunks + 127) / 128)), block(128);
+    const Fp step = fp_pow_u64(w, nchunks), step_inv = fp_pow_u64(w_inv, nchunks);
+    if (zero_aware) hipLaunchKernelGGL(batch_inverse_kernel<true>, grid, block, 0, st, D, nchunks, log_chunk, x0, w, step, step_inv, z, r280 ? 1 : 0, flag, ticket);
+    else hipLaunchKernelGGL(batch_inverse_kernel<false>, grid, block, 0, st, D, nchunks, log_chunk, x0, w, step, step_inv, z, r280 ? 1 : 0, flag, ticket);
+    return hipGetLastError();
+}
+static hipError_t launch_batch_inverse_chunks(hipStream_t st, Fp *D, uint32_t log_N, const Fp &offset, const Fp &w, const Fp &w_inv,
+                                              const Fp &z, bool r280, uint32_t *flag, uint32_t ticket, bool zero_aware) {
+    return launch_batch_inverse_strided(st, D, 1ull << (log_N - batch_inverse_log_chunk(log_N)), batch_inverse_log_chunk(log_N), offset, w, w_inv, z,
+                                        r280, flag, ticket, zero_aware);
+}
+
+// ---- the same table by descent ---------------------------------------------------------------------------------------------------
+// The domain is closed under negation, x_{i + N/2} = -x_i, so its squares are the domain of half the size (offset^2, w^2), and
+//   1 / (x - z) = (x + z) * 1 / (x^2 - z^2).
+// With E_j[i] = 1 / (x_i^(2^j) - z^(2^j)), i < N / 2^j:  E_j[i] = (x_i^(2^j) + z^(2^j)) * E_{j+1}[i mod N / 2^(j+1)].  Only the last,
+// small level E_J is inverted (batch_inverse_kernel on the domain offset^(2^J) <w^(2^J)>, the R280 factor with it); every launch
+// of inverse_descent_kernel then takes two levels at once, in place: with q = N / 2^(j+2), y = x_i^(2^j), c = z^(2^j), i < q,
+//   f0 = (y^2 + c^2) E_{j+2}[i]            f1 = (c^2 - y^2) E_{j+2}[i]                      (E_{j+1}[i], E_{j+1}[i + q])
+//   E_j[i] = (y + c) f0    E_j[i + 2q] = (c - y) f0    E_j[i + q] = (t y + c) f1    E_j[i + 3q] = (c - t y) f1,   t = w^(2^j q), t^2 = -1
+// - a square and eight products for four entries, 2.25 per entry of the level and 3 per entry of the table over all levels, no
+// dependent chain longer than a lane's own powers (a geometric sequence, as in batch_inverse_kernel: lane l takes i = l, l + m, ...),
+// and no inversion.  Level j + 2 sits in D[0, q): lane i reads D[i] before it writes D[i + k q], and nobody else touches either.
+// Entries between levels are the products as they come (normalised, < 2p); the last launch (`final`) writes the fully reduced ones.
+__global__ __launch_bounds__(128) void inverse_descent_kernel(Fp *__restrict__ D, uint64_t q, uint64_t lanes, Fp a, Fp g, Fp step, Fp t, Fp c,
+                                                              Fp c2, int final, const uint32_t *__restrict__ flag, uint32_t ticket) {
+    const uint64_t l = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (l >= lanes || *flag == ticket) return;         // a zero in the last level: the chunked kernel makes the table (launch_batch_inverse)
+    const Fl sl = fl_from_fp(step), tl = fl_from_fp(t), cl = fl_from_fp(c), c2l = fl_from_fp(c2);
+    // y = a g^l in the lazy form (a product there is a third of fp_mul's instructions, and a launch of the lower levels is mostly this)
+    Fl y = fl_from_fp(a), gp = fl_from_fp(g);
+    for (uint64_t b = l; b; b >>= 1) {
+        if (b & 1) y = fl_mul(y, gp);
+        gp = fl_sqr(gp);
+    }
+    Fp e_next = dload(D + l);
+    for (uint64_t i = l; i < q; i += lanes) {
+        const Fl e = fl_from_fp(e_next);
+        if (i + lanes < q) e_next = dload(D + i + lanes);      // the next entry's load runs under this one's products
+        const Fl y2 = fl_sqr(y), ty = fl_mul(y, tl);
+        const Fl f0 = fl_mul(fl_add(y2, c2l), e), f1 = fl_mul(fl_sub_c<2, 1>(c2l, y2), e);
+        const Fl r0 = fl_mul(fl_add(y, cl), f0), r2 = fl_mul(fl_sub_c<2, 1>(cl, y), f0);
+        const Fl r1 = fl_mul(fl_add(ty, cl), f1), r3 = fl_mul(fl_sub_c<2, 1>(cl, ty), f1);
+        if (final) {
+            dstore(D + i, fl_to_fp(r0)); dstore(D + i + q, fl_to_fp(r1)); dstore(D + i + 2 * q, fl_to_fp(r2)); dstore(D + i + 3 * q, fl_to_fp(r3));
+        } else {
+            dstore(D + i, fl_pack(r0)); dstore(D + i + q, fl_pack(r1)); dstore(D + i + 2 * q, fl_pack(r2)); dstore(D + i + 3 * q, fl_pack(r3));
+        }
+        y = fl_mul(y, sl);
+    }
+}
+
+// The last level has 2^L or 2^(L + 1) entries (whichever leaves an even number of levels: a launch takes two), L =
+// BATCH_INVERSE_DESCENT_LAST_LOG: up to there the chunked kernel's time is one chunk's - its inversion, on a chip it does not fill -
+// whatever the size, so a smaller last level only adds launches.  Tables of 2^(L + 3) entries and more descend; below, a last
+// level and one launch are no faster than the chunked kernel alone.  SS_BATCH_INV_DESCENT_LAST_LOG moves L (the parity tests run
+// the descent on small tables with it; tuning).  A launch's lanes: three waves per SIMD, what the kernel's registers admit.
+static constexpr uint32_t BATCH_INVERSE_DESCENT_LAST_LOG = 19, BATCH_INVERSE_DESCENT_LANES = 3 * 64 * 1024;
+static uint32_t batch_inverse_descent_last_log() {
+    if (const char *e = getenv("SS_BATCH_INV_DESCENT_LAST_LOG")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 4 && v <= 40) return v; }
+    return BATCH_INVERSE_DESCENT_LAST_LOG;
+}
+
+// Where a launch reports a zero difference to the launches queued behind it (batch_inverse_kernel).  In the descent the zero is the
+// last level's, x_i^(2^J) = z^(2^J) - which, 2^J <= N, happens exactly when z is a domain point - and would zero every entry of its
+// residue class: the descent's launches then do nothing, and the zero-aware chunked kernel, queued behind them for the whole
+// table, runs only then.  No host round trip.  A launch sequence owns one word of a per-device ring and a ticket no other sequence
+// in flight has; nothing is ever reset.
+static constexpr uint32_t DESCENT_FLAG_SLOTS = 1024, DESCENT_MAX_DEVICES = 64;
+static hipError_t descent_flag(uint32_t **flag, uint32_t *ticket) {
+    static std::mutex mu;
+    static uint32_t *ring[DESCENT_MAX_DEVICES] = {};
+    static std::atomic<uint32_t> next{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= (int)DESCENT_MAX_DEVICES) return hipErrorInvalidDevice;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (!ring[dev]) {
+            uint32_t *p = nullptr;
+            if ((e = hipMalloc((void **)&p, DESCENT_FLAG_SLOTS * sizeof(uint32_t))) != hipSuccess) return e;
+            static const uint32_t zeros[DESCENT_FLAG_SLOTS] = {};
+            if ((e = hipMemcpy(p, zeros, sizeof zeros, hipMemcpyHostToDevice)) != hipSuccess) { (void)hipFree(p); return e; }
+            ring[dev] = p;
+        }
+    }
+    uint32_t k = next.fetch_add(1u) + 1u;
+    if (k == 0) k = next.fetch_add(1u) + 1u;           // 0 is what the ring starts with
+    *ticket = k;
+    *flag = ring[dev] + k % DESCENT_FLAG_SLOTS;
+    return hipSuccess;
+}
+
 hipError_t launch_batch_inverse(hipStream_t st, Fp *D, uint32_t log_N, const Fp &offset, const Fp &w,
                                 const Fp &w_inv, const Fp &z, bool r280) {
-    const uint32_t log_chunk = batch_inverse_log_chunk(log_N);
-    const uint64_t nchunks = 1ull << (log_N - log_chunk);
-    hipLaunchKernelGGL(batch_inverse_kernel, dim3((uint32_t)((nchunks + 127) / 128)), dim3(128), 0, st, D, nchunks,
-                       log_chunk, offset, w, fp_pow_u64(w, nchunks), fp_pow_u64(w_inv, nchunks), z, r280 ? 1 : 0);
-    return hipGetLastError();
+    uint32_t *flag = nullptr, ticket = 0;
+    hipError_t e = descent_flag(&flag, &ticket);
+    if (e != hipSuccess) return e;
+    const uint32_t last_log = batch_inverse_descent_last_log();
+    if (log_N < last_log + 3) {
+        if ((e = launch_batch_inverse_chunks(st, D, log_N, offset, w, w_inv, z, r280, flag, ticket, false)) != hipSuccess) return e;
+        return launch_batch_inverse_chunks(st, D, log_N, offset, w, w_inv, z, r280, flag, ticket, true);
+    }
+    const uint32_t J = (log_N - last_log) & ~1u;                           // even: the last level has 2^last_log or twice as many entries
+    // a[j], g[j], gi[j], c[j]: offset, w, 1 / w, z to the power 2^j
+    Fp a[64], g[64], gi[64], c[64];
+    a[0] = offset; g[0] = w; gi[0] = w_inv; c[0] = z;
+    for (uint32_t j = 1; j <= J; ++j) { a[j] = fp_sqr(a[j - 1]); g[j] = fp_sqr(g[j - 1]); gi[j] = fp_sqr(gi[j - 1]); c[j] = fp_sqr(c[j - 1]); }
+    if ((e = launch_batch_inverse_chunks(st, D, log_N - J, a[J], g[J], gi[J], c[J], r280, flag, ticket, false)) != hipSuccess) return e;
+    for (uint32_t j = J; j >= 2; j -= 2) {
+        const uint32_t lv = j - 2;                                          // the level this launch makes, of 4 q entries
+        const uint64_t q = 1ull << (log_N - j);
+        const uint64_t lanes = q < BATCH_INVERSE_DESCENT_LANES ? q : BATCH_INVERSE_DESCENT_LANES;
+        hipLaunchKernelGGL(inverse_descent_kernel, dim3((uint32_t)((lanes + 127) / 128)), dim3(128), 0, st, D, q, lanes, a[lv], g[lv],
+                           fp_pow_u64(g[lv], lanes), fp_pow_u64(g[lv], q), c[lv], c[lv + 1], lv == 0 ? 1 : 0, flag, ticket);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return launch_batch_inverse_chunks(st, D, log_N, offset, w, w_inv, z, r280, flag, ticket, true);
 }
 
 // D[j] = 1 / (x0 * w^j - z) for j < len: a RANGE of the domain (the row-block form of the sharded prover).  len must be a
@@ -291,9 +421,11 @@ hipError_t launch_batch_inverse_range(hipStream_t st, Fp *D, uint64_t len, const
     const uint32_t log_chunk = BATCH_INVERSE_RANGE_LOG_CHUNK;
     const uint64_t nchunks = len >> log_chunk;
     if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(batch_inverse_kernel, dim3((uint32_t)((nchunks + 127) / 128)), dim3(128), 0, st, D, nchunks,
-                       log_chunk, x0, w, fp_pow_u64(w, nchunks), fp_pow_u64(w_inv, nchunks), z, r280 ? 1 : 0);
-    return hipGetLastError();
+    uint32_t *flag = nullptr, ticket = 0;
+    hipError_t e = descent_flag(&flag, &ticket);
+    if (e != hipSuccess) return e;
+    if ((e = launch_batch_inverse_strided(st, D, nchunks, log_chunk, x0, w, w_inv, z, r280, flag, ticket, false)) != hipSuccess) return e;
+    return launch_batch_inverse_strided(st, D, nchunks, log_chunk, x0, w, w_inv, z, r280, flag, ticket, true);
 }
 
 // ---- DEEP composition -----------------------------------------------------------------

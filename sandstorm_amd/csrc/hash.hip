@@ -56,17 +56,19 @@ __device__ __forceinline__ K64 k_chi64(const K64 &a, const K64 &b, const K64 &c)
 template <int N>
 __device__ __forceinline__ K64 k_xrot(const K64 &a, const K64 &d) { return k_rotl<N>(k_xor(a, d)); }
 
-__device__ __forceinline__ void keccak_f1600(uint64_t st[25]) {
-    K64 s[25];
-#pragma unroll
-    for (int i = 0; i < 25; ++i) s[i] = k_split(st[i]);
+// theta of one round: the five column sums of the whole state -> d0 .. d4
+#define KECCAK_THETA(s)                                                                                                 \
+    const K64 c0 = k_xor5(s[0], s[5], s[10], s[15], s[20]), c1 = k_xor5(s[1], s[6], s[11], s[16], s[21]);               \
+    const K64 c2 = k_xor5(s[2], s[7], s[12], s[17], s[22]), c3 = k_xor5(s[3], s[8], s[13], s[18], s[23]);               \
+    const K64 c4 = k_xor5(s[4], s[9], s[14], s[19], s[24]);                                                             \
+    const K64 d0 = k_xor(c4, k_rotl<1>(c1)), d1 = k_xor(c0, k_rotl<1>(c2)), d2 = k_xor(c1, k_rotl<1>(c3));              \
+    const K64 d3 = k_xor(c2, k_rotl<1>(c4)), d4 = k_xor(c3, k_rotl<1>(c0));
+
+// rounds 0 .. nrounds - 1 on the split state
+__device__ __forceinline__ void keccak_rounds(K64 (&s)[25], int nrounds) {
 #pragma unroll 1
-    for (int round = 0; round < 24; ++round) {
-        const K64 c0 = k_xor5(s[0], s[5], s[10], s[15], s[20]), c1 = k_xor5(s[1], s[6], s[11], s[16], s[21]);
-        const K64 c2 = k_xor5(s[2], s[7], s[12], s[17], s[22]), c3 = k_xor5(s[3], s[8], s[13], s[18], s[23]);
-        const K64 c4 = k_xor5(s[4], s[9], s[14], s[19], s[24]);
-        const K64 d0 = k_xor(c4, k_rotl<1>(c1)), d1 = k_xor(c0, k_rotl<1>(c2)), d2 = k_xor(c1, k_rotl<1>(c3));
-        const K64 d3 = k_xor(c2, k_rotl<1>(c4)), d4 = k_xor(c3, k_rotl<1>(c0));
+    for (int round = 0; round < nrounds; ++round) {
+        KECCAK_THETA(s)
         // theta + rho + pi into b
         const K64 b0 = k_xor(s[0], d0);
         const K64 b10 = k_xrot<1>(s[1], d1), b20 = k_xrot<62>(s[2], d2), b5 = k_xrot<28>(s[3], d3);
@@ -86,8 +88,37 @@ __device__ __forceinline__ void keccak_f1600(uint64_t st[25]) {
         const uint64_t rc = KECCAK_RC[round];
         s[0].lo ^= (uint32_t)rc; s[0].hi ^= (uint32_t)(rc >> 32);
     }
+}
+
+// The whole permutation.  For callers that go on absorbing (every block of a message but its last) or read the state
+// past lane 3; the proof-of-work kernels stay on it too: they are no part of the commitment path.
+__device__ __forceinline__ void keccak_f1600(uint64_t st[25]) {
+    K64 s[25];
+#pragma unroll
+    for (int i = 0; i < 25; ++i) s[i] = k_split(st[i]);
+    keccak_rounds(s, 24);
 #pragma unroll
     for (int i = 0; i < 25; ++i) st[i] = k_join(s[i]);
+}
+
+// The permutation before a 32-byte squeeze: only st[0..3] are read afterwards (keccak_store_digest), and lanes 0..3 of
+// round 23's output are chi of row 0 of its b - which needs theta's column sums of the whole state, but rho / pi / chi
+// for b0 .. b4 alone.  20 rotations and 21 chi lanes less than the full round; st[4..24] are left as round 22 made them.
+__device__ __forceinline__ void keccak_f1600_squeeze4(uint64_t st[25]) {
+    K64 s[25];
+#pragma unroll
+    for (int i = 0; i < 25; ++i) s[i] = k_split(st[i]);
+    keccak_rounds(s, 23);
+    {
+        KECCAK_THETA(s)
+        const K64 b0 = k_xor(s[0], d0), b1 = k_xrot<44>(s[6], d1), b2 = k_xrot<43>(s[12], d2);
+        const K64 b3 = k_xrot<21>(s[18], d3), b4 = k_xrot<14>(s[24], d4);
+        s[0] = k_chi64(b0, b1, b2); s[1] = k_chi64(b1, b2, b3); s[2] = k_chi64(b2, b3, b4); s[3] = k_chi64(b3, b4, b0);
+        const uint64_t rc = 0x8000000080008008ull;              // KECCAK_RC[23]
+        s[0].lo ^= (uint32_t)rc; s[0].hi ^= (uint32_t)(rc >> 32);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) st[i] = k_join(s[i]);
 }
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
@@ -106,21 +137,75 @@ __device__ __forceinline__ void keccak_store_digest(const uint64_t s[25], uint8_
     q[1] = make_ulonglong2(o2, o3);
 }
 
-// Absorb `nelem` felts fetched through `fetch(c)` (pointer to the 4 u64 limbs).
+// Absorb `nelem` felts fetched through `fetch(c)` (pointer to the 4 u64 limbs) - the path of every width that has no
+// instantiation of keccak_hash_felts below.  Blocks before the last take the whole permutation (the state is absorbed into
+// again), the last one the squeeze form: s[0..3] are the digest, the rest of s is not the permuted state.
 template <typename Fetch>
 __device__ __forceinline__ void keccak_absorb_felts(uint64_t s[25], uint32_t nelem, Fetch fetch) {
     const uint32_t data_lanes = 4 * nelem;            // pad byte 0x01 sits in lane `data_lanes`
     const uint32_t nblocks = data_lanes / 17 + 1;
-    for (uint32_t blk = 0; blk < nblocks; ++blk) {
+    auto absorb = [&](uint32_t blk) {
 #pragma unroll
         for (int pos = 0; pos < 17; ++pos) {
             const uint32_t lane = blk * 17 + pos;
             if (lane < data_lanes) s[pos] ^= felt_msg_lane(fetch(lane >> 2), lane & 3);
             else if (lane == data_lanes) s[pos] ^= 0x01ull;
         }
-        if (blk == nblocks - 1) s[16] ^= 0x8000000000000000ull;
+    };
+    for (uint32_t blk = 0; blk + 1 < nblocks; ++blk) {
+        absorb(blk);
         keccak_f1600(s);
     }
+    absorb(nblocks - 1);
+    s[16] ^= 0x8000000000000000ull;
+    keccak_f1600_squeeze4(s);
+}
+
+// The same for a width known at compile time: e[c] points at felt c of the message.  A felt is two 16-byte loads; which
+// sponge lane takes which message lane, where the pad byte sits and which block is the last are all constants, so
+// absorbing is one xor per message lane and nothing else.
+template <int NC, int BLK>
+__device__ __forceinline__ void keccak_absorb_block(uint64_t s[25], const uint64_t (&m)[4 * NC]) {
+    constexpr int DL = 4 * NC, NB = DL / 17 + 1;
+    if constexpr (BLK < NB) {
+#pragma unroll
+        for (int pos = 0; pos < 17; ++pos) {
+            constexpr int base = BLK * 17;
+            if (base + pos < DL) s[pos] ^= m[base + pos < DL ? base + pos : 0];
+            else if (base + pos == DL) s[pos] ^= 0x01ull;
+        }
+        if constexpr (BLK == NB - 1) {
+            s[16] ^= 0x8000000000000000ull;
+            keccak_f1600_squeeze4(s);                  // the digest is all that is read of it
+        } else {
+            keccak_f1600(s);                           // absorbed into again: the whole state
+        }
+        keccak_absorb_block<NC, BLK + 1>(s, m);
+    }
+}
+// m[4 c .. 4 c + 3]: the message lanes of felt c - as little-endian words, its 32 big-endian bytes
+template <int NC>
+__device__ __forceinline__ void keccak_load_felts(uint64_t (&m)[4 * NC], const uint4 *const (&e)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const uint4 a = e[c][0], b = e[c][1];          // limbs 0..3, 4..7: message lane k is the byte-swapped 64-bit limb 3 - k
+        m[4 * c + 0] = bswap64(((uint64_t)b.w << 32) | b.z);
+        m[4 * c + 1] = bswap64(((uint64_t)b.y << 32) | b.x);
+        m[4 * c + 2] = bswap64(((uint64_t)a.w << 32) | a.z);
+        m[4 * c + 3] = bswap64(((uint64_t)a.y << 32) | a.x);
+    }
+}
+template <int NC>
+__device__ __forceinline__ void keccak_hash_lanes(uint64_t s[25], const uint64_t (&m)[4 * NC]) {
+#pragma unroll
+    for (int i = 0; i < 25; ++i) s[i] = 0;
+    keccak_absorb_block<NC, 0>(s, m);
+}
+template <int NC>
+__device__ __forceinline__ void keccak_hash_felts(uint64_t s[25], const uint4 *const (&e)[NC]) {
+    uint64_t m[4 * NC];
+    keccak_load_felts<NC>(m, e);
+    keccak_hash_lanes<NC>(s, m);
 }
 
 // brev_bits != 0: digest i is that of matrix row bitrev(i) over brev_bits bits - the commitment order of the
@@ -141,6 +226,25 @@ __global__ __launch_bounds__(256) void keccak_rows_kernel(ConstColPtrs cols, uin
         keccak_absorb_felts(s, ncols, [&](uint32_t c) {
             return reinterpret_cast<const uint64_t *>(cols.p[c]) + 4 * row;
         });
+        keccak_store_digest(s, out + 32 * digest_slot(row, brev_bits), mask20 != 0);
+    }
+}
+
+// The widths the provers commit to - 9 base-trace columns, 2 composition columns, 8 (and 2, 4) felts of a FRI row, 1, 7
+// and 10 of the other layouts - as instantiations; keccak_rows_kernel above serves every other width.
+template <int NC>
+__global__ __launch_bounds__(256) void keccak_rows_w_kernel(ConstColPtrs cols, uint64_t nrows, uint8_t *__restrict__ out, int mask20,
+                                                            uint32_t brev_bits) {
+    const uint4 *col[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) col[c] = reinterpret_cast<const uint4 *>(cols.p[c]);
+    for (uint64_t row = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; row < nrows;
+         row += (uint64_t)gridDim.x * blockDim.x) {
+        const uint4 *e[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) e[c] = col[c] + 2 * row;
+        uint64_t s[25];
+        keccak_hash_felts<NC>(s, e);
         keccak_store_digest(s, out + 32 * digest_slot(row, brev_bits), mask20 != 0);
     }
 }
@@ -169,7 +273,7 @@ __global__ __launch_bounds__(256) void keccak_rows_u64_kernel(ConstColPtrs segs,
                 } else if (lane == data_lanes) s[pos] ^= 0x01ull;
             }
             if (blk == nblocks - 1) s[16] ^= 0x8000000000000000ull;
-            keccak_f1600(s);
+            keccak_f1600(s);                            // the 64-bit field's rows: one call for every block, the whole permutation
         }
         keccak_store_digest(s, out + 32 * row, false);
     }
@@ -183,16 +287,27 @@ __global__ void gather_rows_u64_kernel(ConstColPtrs segs, uint32_t nseg, uint32_
     out[t] = reinterpret_cast<const uint64_t *>(segs.p[s])[idx[j] * seg_len + e];
 }
 
-// leaf level of UnhashedLeafConfig: H::hash_elements([l0, l1]) (merkle/mod.rs:426-428)
-__global__ __launch_bounds__(256) void keccak_felt_pairs_kernel(const uint64_t *__restrict__ felts, uint64_t count,
-                                                                uint8_t *__restrict__ out, int mask20) {
+// leaf level of UnhashedLeafConfig: H::hash_elements([l0, l1]) (merkle/mod.rs:426-428).
+// brev_bits == 0: out[k] = H(felts[2k], felts[2k + 1]).  brev_bits == log2(count) != 0, the ordered mode: the leaves are the
+// bit-reversed image of `felts` (2 count of them), whose siblings 2k and 2k + 1 are the natural rows r = bitrev(k) and
+// r + count - lane r reads both coalesced and scatters the one digest to slot bitrev(r), as the row kernels do.
+// leaves != null: the pair's leaf slots (the felts as 32 big-endian bytes, 64 adjacent bytes at leaf 2 slot) are written here
+// too - the message lanes are those bytes - so the tree build makes no pass of its own over the column for them.
+__global__ __launch_bounds__(256) void keccak_felt_pairs_kernel(const uint4 *__restrict__ felts, uint64_t count, uint8_t *__restrict__ out,
+                                                                uint8_t *__restrict__ leaves, int mask20, uint32_t brev_bits) {
     for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < count;
          k += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t s[25];
+        const uint4 *e[2] = {felts + 2 * (brev_bits ? k : 2 * k), felts + 2 * (brev_bits ? k + count : 2 * k + 1)};
+        const uint64_t slot = digest_slot(k, brev_bits);
+        uint64_t s[25], m[8];
+        keccak_load_felts<2>(m, e);
+        if (leaves) {
+            ulonglong2 *q = reinterpret_cast<ulonglong2 *>(leaves + 64 * slot);
 #pragma unroll
-        for (int i = 0; i < 25; ++i) s[i] = 0;
-        keccak_absorb_felts(s, 2, [&](uint32_t c) { return felts + 4 * (2 * k + c); });
-        keccak_store_digest(s, out + 32 * k, mask20 != 0);
+            for (int i = 0; i < 4; ++i) q[i] = make_ulonglong2(m[2 * i], m[2 * i + 1]);
+        }
+        keccak_hash_lanes<2>(s, m);
+        keccak_store_digest(s, out + 32 * slot, mask20 != 0);
     }
 }
 
@@ -209,7 +324,7 @@ __global__ __launch_bounds__(256) void keccak_pairs_kernel(const uint8_t *__rest
 #pragma unroll
         for (int i = 9; i < 25; ++i) s[i] = 0;
         s[16] = 0x8000000000000000ull;
-        keccak_f1600(s);
+        keccak_f1600_squeeze4(s);                       // one block, then the digest
         keccak_store_digest(s, out + 32 * k, mask20 != 0);
     }
 }
@@ -304,13 +419,22 @@ __global__ __launch_bounds__(256) void blake2s_rows_kernel(ConstColPtrs cols, ui
     }
 }
 
-__global__ __launch_bounds__(256) void blake2s_felt_pairs_kernel(const Fp *__restrict__ felts, uint64_t count,
-                                                                 uint8_t *__restrict__ out, int mask20) {
+__device__ __forceinline__ void store_felt_be(const Fp &e, uint8_t *out) {
+    uint4 *q = reinterpret_cast<uint4 *>(out);
+    q[0] = make_uint4(bswap32(e.v[7]), bswap32(e.v[6]), bswap32(e.v[5]), bswap32(e.v[4]));
+    q[1] = make_uint4(bswap32(e.v[3]), bswap32(e.v[2]), bswap32(e.v[1]), bswap32(e.v[0]));
+}
+// brev_bits, leaves: the ordered mode and the leaf slots of keccak_felt_pairs_kernel
+__global__ __launch_bounds__(256) void blake2s_felt_pairs_kernel(const Fp *__restrict__ felts, uint64_t count, uint8_t *__restrict__ out,
+                                                                 uint8_t *__restrict__ leaves, int mask20, uint32_t brev_bits) {
     for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < count;
          k += (uint64_t)gridDim.x * blockDim.x) {
+        const Fp e0 = load_fp(brev_bits ? felts + k : felts + 2 * k), e1 = load_fp(brev_bits ? felts + k + count : felts + 2 * k + 1);
+        const uint64_t slot = digest_slot(k, brev_bits);
+        if (leaves) { store_felt_be(e0, leaves + 64 * slot); store_felt_be(e1, leaves + 64 * slot + 32); }
         uint32_t h[8];
-        blake2s_hash_felts(h, 2, [&](uint32_t c) { return load_fp(felts + 2 * k + c); });
-        blake2s_store_digest(h, out + 32 * k, mask20 != 0);
+        blake2s_hash_felts(h, 2, [&](uint32_t c) { return c ? e1 : e0; });
+        blake2s_store_digest(h, out + 32 * slot, mask20 != 0);
     }
 }
 
@@ -331,12 +455,8 @@ __global__ __launch_bounds__(256) void blake2s_pairs_kernel(const uint8_t *__res
 __global__ __launch_bounds__(256) void felts_to_be_kernel(const Fp *__restrict__ felts, uint64_t count,
                                                           uint8_t *__restrict__ out) {
     for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < count;
-         k += (uint64_t)gridDim.x * blockDim.x) {
-        Fp e = load_fp(felts + k);
-        uint4 *q = reinterpret_cast<uint4 *>(out + 32 * k);
-        q[0] = make_uint4(bswap32(e.v[7]), bswap32(e.v[6]), bswap32(e.v[5]), bswap32(e.v[4]));
-        q[1] = make_uint4(bswap32(e.v[3]), bswap32(e.v[2]), bswap32(e.v[1]), bswap32(e.v[0]));
-    }
+         k += (uint64_t)gridDim.x * blockDim.x)
+        store_felt_be(load_fp(felts + k), out + 32 * k);
 }
 
 // ------------------------------------------------------------ PoW grinding
@@ -357,7 +477,7 @@ __global__ void pow_prefix_kernel(int coin_kind, Digest32 digest, uint32_t bits,
         s[1] = digest.w[0]; s[2] = digest.w[1]; s[3] = digest.w[2]; s[4] = digest.w[3];
         s[5] = (uint64_t)(bits & 0xffu) | (0x01ull << 8);
         s[16] = 0x8000000000000000ull;
-        keccak_f1600(s);
+        keccak_f1600(s);                                // once per proof: the whole permutation
         prefix[0] = s[0]; prefix[1] = s[1]; prefix[2] = s[2]; prefix[3] = s[3];
     } else {
         uint32_t h[8], m[16];
@@ -390,7 +510,7 @@ __global__ __launch_bounds__(256) void pow_grind_kernel(int coin_kind, const uin
             s[4] = bswap64(nonce);
             s[5] = 0x01ull;
             s[16] = 0x8000000000000000ull;
-            keccak_f1600(s);
+            keccak_f1600(s);                            // the grinding loop is no part of the commitment path: unchanged
             lead = bswap64(s[0]);
         } else {
             uint32_t h[8], m[16];
@@ -575,9 +695,15 @@ hipError_t launch_gather_rows_u64(hipStream_t st, const ConstColPtrs &segs, uint
 hipError_t launch_hash_rows(hipStream_t st, int kind, const ConstColPtrs &cols, uint32_t ncols,
                             uint64_t nrows, uint32_t brev_bits, uint8_t *digests) {
     const uint32_t grid = grid_for(nrows, 256, 1u << 20);
-    if (kind == 0 || kind == 1)
-        hipLaunchKernelGGL(keccak_rows_kernel, dim3(grid), dim3(256), 0, st, cols, ncols, nrows, digests, kind == 1, brev_bits);
-    else
+    if (kind == 0 || kind == 1) {
+        const int m20 = kind == 1;
+        switch (ncols) {
+#define SS_KECCAK_ROWS_W(NC) case NC: hipLaunchKernelGGL(keccak_rows_w_kernel<NC>, dim3(grid), dim3(256), 0, st, cols, nrows, digests, m20, brev_bits); break;
+            SS_KECCAK_ROWS_W(1) SS_KECCAK_ROWS_W(2) SS_KECCAK_ROWS_W(4) SS_KECCAK_ROWS_W(7) SS_KECCAK_ROWS_W(8) SS_KECCAK_ROWS_W(9) SS_KECCAK_ROWS_W(10)
+#undef SS_KECCAK_ROWS_W
+            default: hipLaunchKernelGGL(keccak_rows_kernel, dim3(grid), dim3(256), 0, st, cols, ncols, nrows, digests, m20, brev_bits);
+        }
+    } else
         hipLaunchKernelGGL(blake2s_rows_kernel, dim3(grid), dim3(256), 0, st, cols, ncols, nrows, digests, kind == 3, brev_bits);
     return hipGetLastError();
 }
@@ -606,13 +732,19 @@ hipError_t launch_hash_pairs(hipStream_t st, int kind, const uint8_t *in, uint64
         hipLaunchKernelGGL(blake2s_pairs_kernel, dim3(grid), dim3(256), 0, st, in, count, out, kind == 3);
     return hipGetLastError();
 }
-hipError_t launch_hash_felt_pairs(hipStream_t st, int kind, const Fp *felts, uint64_t count, uint8_t *out) {
-    const uint32_t grid = grid_for(count, 256, 1u << 20);
+static inline uint32_t log2_exact(uint64_t n) {
+    uint32_t l = 0;
+    while ((1ull << l) < n) ++l;
+    return l;
+}
+hipError_t launch_hash_felt_pairs(hipStream_t st, int kind, const Fp *felts, uint64_t count, bool bitrev, uint8_t *out, uint8_t *leaves) {
+    if (bitrev && (count & (count - 1))) return hipErrorInvalidValue;
+    const uint32_t grid = grid_for(count, 256, 1u << 20), brev_bits = bitrev ? log2_exact(count) : 0;       // one pair: both orders are the same
     if (kind == 0 || kind == 1)
         hipLaunchKernelGGL(keccak_felt_pairs_kernel, dim3(grid), dim3(256), 0, st,
-                           reinterpret_cast<const uint64_t *>(felts), count, out, kind == 1);
+                           reinterpret_cast<const uint4 *>(felts), count, out, leaves, kind == 1, brev_bits);
     else
-        hipLaunchKernelGGL(blake2s_felt_pairs_kernel, dim3(grid), dim3(256), 0, st, felts, count, out, kind == 3);
+        hipLaunchKernelGGL(blake2s_felt_pairs_kernel, dim3(grid), dim3(256), 0, st, felts, count, out, leaves, kind == 3, brev_bits);
     return hipGetLastError();
 }
 hipError_t launch_felts_to_be(hipStream_t st, const Fp *felts, uint64_t count, uint8_t *out) {

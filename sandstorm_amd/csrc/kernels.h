@@ -44,8 +44,10 @@ hipError_t launch_hash_rows(hipStream_t st, int kind, const ConstColPtrs &cols, 
 hipError_t launch_bitrev_copy(hipStream_t st, const Fp *src, uint32_t log_n, Fp *dst);
 // one Merkle level: out[k] = H(in[2k] || in[2k+1]) for k < count (64-byte messages)
 hipError_t launch_hash_pairs(hipStream_t st, int kind, const uint8_t *in, uint64_t count, uint8_t *out);
-// leaf level of single-column trees: out[k] = H::hash_elements([felt[2k], felt[2k+1]])
-hipError_t launch_hash_felt_pairs(hipStream_t st, int kind, const Fp *felts, uint64_t count, uint8_t *out);
+// leaf level of single-column trees: out[k] = H::hash_elements([leaf[2k], leaf[2k+1]]); leaf[i] = felts[i], or, bitrev (count a
+// power of two), felts[bitrev(i)] over the 2 count felts - read in natural order, the digests scattered.  leaves (may be null):
+// the 2 count leaf slots of the node array, leaf i as its Montgomery big-endian bytes, written by the same launch
+hipError_t launch_hash_felt_pairs(hipStream_t st, int kind, const Fp *felts, uint64_t count, bool bitrev, uint8_t *out, uint8_t *leaves);
 // felt leaves -> Montgomery big-endian bytes (leaf slots of the node array)
 hipError_t launch_felts_to_be(hipStream_t st, const Fp *felts, uint64_t count, uint8_t *out);
 hipError_t launch_pow_prefix(hipStream_t st, int coin_kind, const uint8_t digest[32], uint32_t bits,
