@@ -514,7 +514,10 @@ enum { SS_TRACE_ERR_MISSING_CELL = 1,        /* the run reads a cell memory.bin 
        SS_TRACE_ERR_PEDERSEN_INFINITY = 8192,  /* ss_trace_pedersen: a partial sum meets its constant point (see there) */
        SS_TRACE_ERR_PEDERSEN_INSTANCE = 16384, /* ss_trace_pedersen: an instance's index is beyond the blocks, or an input has a bit from 252 up: skipped */
        SS_TRACE_ERR_BITWISE_INSTANCE = 32768,  /* ss_trace_bitwise: the same, for a bitwise instance                    */
-       SS_TRACE_ERR_POSEIDON_INSTANCE = 65536 }; /* ss_trace_poseidon: the same, for a Poseidon instance                */
+       SS_TRACE_ERR_POSEIDON_INSTANCE = 65536, /* ss_trace_poseidon: the same, for a Poseidon instance                  */
+       SS_TRACE_ERR_EC_OP_INSTANCE = 131072, /* ss_trace_ec_op: the same, for an EC-op instance                        */
+       SS_TRACE_ERR_EC_OP_DIVISOR = 262144,  /* ss_trace_ec_op: a doubling of Q whose y is zero (the tangent's slope divides by it) */
+       SS_TRACE_ERR_EC_OP_MEETS = 524288 };  /* ss_trace_ec_op: a partial sum shares its x with its step's point (see there) */
 /* memory.bin on the device: d_records = the file's bytes (n_records x (u64 address, 32-byte little-endian word), uploaded by
  * the caller) -> d_image[address] as 4 x u64; cells the file does not name are marked (all-ones: not a field element).
  * cells: entries of d_image; records beyond it are dropped (no address above n / 2 can be accessed by a valid run). */
@@ -614,6 +617,37 @@ typedef struct {
 ss_status ss_trace_poseidon(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_poseidon_layout *layout,
                             const uint64_t *d_round_keys, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows,
                             uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
+/* A GIVEN EC-op instance's cells from P, Q and m, computed on the device (builtins/src/ec_op/mod.rs:40-130; starknet trace.rs:707-777)
+ * - no template, 168 bytes per instance.  d_instances: n_given records of 21 u64 = index, P.x[4], P.y[4], Q.x[4], Q.y[4], m[4]
+ * (canonical little-endian limbs below 2^252); instance `index` owns rows [index * block_rows, (index + 1) * block_rows) of the
+ * columns (col_rows felts each; n_blocks * block_rows <= col_rows).  For each of the 256 steps j, row off_* + row_stride * j of the
+ * block in column `col` gets the doubling point 2^j Q (off_dbl_x, off_dbl_y) with its tangent's slope (3 x^2 + 1) / (2 y)
+ * (off_dbl_slope), the partial sum before the step - P plus the 2^i Q of the set bits i < j of m - (off_sum_x, off_sum_y), the suffix
+ * m >> j (off_suffix) and, for j != 255 only, the chord's slope (off_slope; zero where bit j is clear) and 1 / (partial.x - point.x)
+ * (off_x_diff_inv): those two cells of step 255 are the ECDSA section's and are neither written nor read.  Then the cells
+ * bit251 && bit196 (off_flag2) and bit251 && bit196 && bit192 (off_flag3) of m, and the seven memory-pool pairs
+ * (addr_begin + 7 * index + k, value) of P.x, P.y, Q.x, Q.y, m, R.x, R.y - R the partial sum at step 255 - at rows off_pair[k] (even) of
+ * col_pool, their integer addresses in d_pool_addr[row / 2] (col_rows / 2 u32).  All values Montgomery felts, bit-identical to the
+ * host generator's.  No cell of the columns ever holds an intermediate value: the chains' scratch is LDS, and the doubling points are
+ * read back from their own cells once they are final.
+ * Call it AFTER ss_trace_builtin has laid the ECDSA templates and the EC-op dummy instance's template over all blocks: it
+ * overwrites the given ones.  The indices must be distinct.
+ * Refused with an error (nothing launched): NULL pointers (also with n_given = 0), blocks that do not fit the columns, a column
+ * >= ncols, a cell that leaves its block, an odd pool offset.  Found on the device, as bits of d_status: an index >= n_blocks or an
+ * input with a bit from 252 up - skipped, nothing written (SS_TRACE_ERR_EC_OP_INSTANCE); a doubling of Q whose y is zero
+ * (SS_TRACE_ERR_EC_OP_DIVISOR: the host generator's "a curve step divides by zero"); a partial sum that shares its x with its step's
+ * point, at any of the 256 steps, bit set or clear (SS_TRACE_ERR_EC_OP_MEETS: "a partial sum meets the fixed point").  After either of
+ * the last two the instance's cells are unfinished and the caller must refuse the generation - host/device_trace.hpp does, the divisor
+ * first, as the host generator reaches it first. */
+typedef struct {
+    uint32_t col, row_stride;                                                             /* step j: row off + row_stride * j (64 starknet) */
+    uint32_t off_dbl_x, off_dbl_y, off_dbl_slope, off_sum_x, off_sum_y, off_suffix, off_slope, off_x_diff_inv;
+    uint32_t off_flag2, off_flag3;                                                        /* (col) */
+    uint32_t col_pool, off_pair[7];                                                       /* P.x, P.y, Q.x, Q.y, m, R.x, R.y */
+} ss_trace_ec_op_layout;
+ss_status ss_trace_ec_op(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_ec_op_layout *layout,
+                         const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr,
+                         uint32_t *d_status);
 /* The 16-bit range-check pool (utils.rs:357-380; starknet trace.rs:142-165, 246-292, 388-426).  The caller counts the pool's
  * values (65536 bins: the instructions' offsets, the builtin's parts) and hands over
  *   d_first[j], j <= rc_hi - rc_lo + 1: ordered values before value rc_lo + j (every value of [rc_lo, rc_hi] max(count, 1) times),

@@ -167,7 +167,8 @@ enum { TRACE_ST_ERRORS = 0, TRACE_ST_WHERE = 1, TRACE_ST_ZEROS = 2, TRACE_ST_ONE
 enum { TRACE_ERR_MISSING_CELL = 1, TRACE_ERR_NOT_INSTRUCTION = 2, TRACE_ERR_BAD_OP1_SOURCE = 4, TRACE_ERR_BAD_RES_LOGIC = 8, TRACE_ERR_NOT_AN_ADDRESS = 16,
        TRACE_ERR_ADDRESS_RANGE = 32, TRACE_ERR_PUBLIC_ZERO = 64, TRACE_ERR_PUBLIC_CELLS = 128, TRACE_ERR_NO_ONES = 256, TRACE_ERR_NOT_SINGLE_VALUED = 512,
        TRACE_ERR_NOT_CONTINUOUS = 1024, TRACE_ERR_TOO_MANY_GAPS = 2048, TRACE_ERR_FILL = 4096, TRACE_ERR_PEDERSEN_INFINITY = 8192,
-       TRACE_ERR_PEDERSEN_INSTANCE = 16384, TRACE_ERR_BITWISE_INSTANCE = 32768, TRACE_ERR_POSEIDON_INSTANCE = 65536 };
+       TRACE_ERR_PEDERSEN_INSTANCE = 16384, TRACE_ERR_BITWISE_INSTANCE = 32768, TRACE_ERR_POSEIDON_INSTANCE = 65536,
+       TRACE_ERR_EC_OP_INSTANCE = 131072, TRACE_ERR_EC_OP_DIVISOR = 262144, TRACE_ERR_EC_OP_MEETS = 524288 };
 hipError_t launch_trace_memory_image(hipStream_t st, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells);
 hipError_t launch_trace_cpu(hipStream_t st, const TraceLayout &L, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells,
                             const Fp &pad_value, uint64_t rc_fill, Fp *flags, Fp *npc, Fp *rc, Fp *aux, uint32_t *d_pool_addr, uint32_t *d_status);
@@ -211,6 +212,15 @@ static constexpr uint32_t TRACE_POSEIDON_FULL_ROUNDS = 8, TRACE_POSEIDON_PARTIAL
 // d_round_keys: TRACE_POSEIDON_ROUNDS x 3 Montgomery felts in the order the rounds take them (4 full, 83 partial, 4 full)
 hipError_t launch_trace_poseidon(hipStream_t st, const ColPtrs &cols, const TracePoseidonLayout &L, const Fp *d_round_keys, const uint64_t *d_instances,
                                  uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
+// an EC-op instance's cells from P, Q, m (= ss_trace_ec_op_layout): step j of the 256 at row off_* + row_stride * j of its block in column
+// col - the doubling point 2^j Q with its tangent's slope, the partial sum before the step, m >> j, and for j != 255 the chord's slope
+// and 1 / (partial.x - point.x); the two flag cells; the seven memory-pool pairs (P.x, P.y, Q.x, Q.y, m, R.x, R.y)
+struct TraceEcOpLayout {
+    uint32_t col, row_stride, off_dbl_x, off_dbl_y, off_dbl_slope, off_sum_x, off_sum_y, off_suffix, off_slope, off_x_diff_inv;
+    uint32_t off_flag2, off_flag3, col_pool, off_pair[7];
+};
+hipError_t launch_trace_ec_op(hipStream_t st, const ColPtrs &cols, const TraceEcOpLayout &L, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks,
+                              uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
 hipError_t launch_trace_ordered_memory(hipStream_t st, const TraceMemoryArgs &m, uint32_t *scratch);
 
 // ---- goldilocks.hip (the 64-bit field variant)

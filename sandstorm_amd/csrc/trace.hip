@@ -19,6 +19,8 @@
 //                         top segments, five memory-pool pairs
 //   trace_poseidon_kernel the GIVEN Poseidon instances from their three inputs (104 bytes each): one lane per instance walks the 91
 //                         rounds and stores every S-box input with its square (the S-box's own intermediate)
+//   trace_ec_op_kernel    the GIVEN EC-op instances from P, Q, m (168 bytes each): one wave per instance - the doubling chain and the
+//                         multiply-add chain in Jacobian coordinates on one lane, then four steps a lane with one inversion each
 //   trace_rc_*            the range-check builtin's parts and the pool's ordered values / padding (utils.rs:357-380):
 //                         runs located by binary search in a prefix array of the 65536-bin histogram
 //   trace_runs_kernel     the diluted pool's ordered column the same way
@@ -461,6 +463,196 @@ __global__ __launch_bounds__(64) void trace_poseidon_kernel(ColPtrs cols, TraceP
     ped_pool_pair(pool, pool_addr, base + L.off_pair[5], addr0 + 5, s.c);
 }
 
+// ------------------------------------------------------------------------------------------------ EC-op instances from their inputs
+// A GIVEN EC-op instance (index, P, Q, m: 21 u64) -> the cells the host generator's EC-op section writes for it (host/trace_starknet.cpp
+// doubling_steps / ec_mad_steps; builtins/src/ec_op/mod.rs:40-130): per step j < 256 the doubling point 2^j Q with its tangent's slope,
+// the partial sum P + the 2^i Q of the set bits i < j of m, the suffix m >> j and - for j != 255, the ECDSA section owns those two
+// cells of the last step - the chord's slope and 1 / (partial.x - point.x); the two flag cells; the seven memory-pool pairs.
+// One workgroup of ONE wave per instance: the two chains are sequential - a wave per instance keeps every instance of a 2^20-step
+// statement (1024) resident at once, a wave to a SIMD - and run on lane 0 in Jacobian coordinates into LDS; what surrounds them is
+// 256-wide, four steps a lane, each step with ONE inversion of its own (safegcd: no batching, no scan, no scratch outside LDS):
+//   wg_doubling_steps   lane 0: the 256 Jacobian doublings; per step: 1 / (2 Y Z) gives both 1 / Z (the affine point) and
+//                       1 / (2 y) = Z^4 / (2 Y Z) (the slope) - straight into the cells
+//   wg_ec_mad_steps     lane 0: one mixed addition per set bit i (the affine point read back from its cell), the sum AFTER bit i in LDS
+//                       slot i; per step j: the sum BEFORE it is the one after the last set bit below j, h = x_j Z^2 - X =
+//                       -(partial.x - point.x) Z^2, and 1 / (h Z) gives 1 / Z and 1 / (partial.x - point.x)
+// These have the parameters of the host's doubling_steps(p) and ec_mad_steps(x, point, start, max_doublings): an ECDSA instance is
+// three of the second and two of the first.  A doubling whose y is zero sets TRACE_ERR_EC_OP_DIVISOR, a partial sum that shares its
+// x with its step's point - set bit or clear - TRACE_ERR_EC_OP_MEETS; the workgroup leaves the instance unfinished then (only cells of
+// its own steps were touched) and the generation is refused.  An index beyond the blocks or an input with a bit from 252 up: skipped
+// with TRACE_ERR_EC_OP_INSTANCE, nothing written.
+constexpr u32 EC_STEPS = 256, EC_LANES = 64;
+struct EcShared { Fp a[EC_STEPS], b[EC_STEPS], c[EC_STEPS]; u64 rec[21]; u32 divisor, meets; };
+struct EcJac { Fp X, Y, Z; };
+__device__ __forceinline__ EcJac ec_jac_double(const EcJac &p) {     // a = 1: M = 3 X^2 + Z^4, S = 4 X Y^2 (host/trace_common.hpp jac_double)
+    const Fp xx = fp_sqr(p.X), yy = fp_sqr(p.Y), zz = fp_sqr(p.Z);
+    const Fp s4 = fp_dbl(fp_dbl(fp_mul(p.X, yy)));
+    const Fp m = fp_add(fp_add(fp_dbl(xx), xx), fp_sqr(zz));
+    EcJac r;
+    r.X = fp_sub(fp_sqr(m), fp_dbl(s4));
+    r.Y = fp_sub(fp_mul(m, fp_sub(s4, r.X)), fp_dbl(fp_dbl(fp_dbl(fp_sqr(yy)))));
+    r.Z = fp_dbl(fp_mul(p.Y, p.Z));
+    return r;
+}
+// p, 2 p, 4 p, ... with the tangents' slopes: x, y, slope of step j to cx / cy / cslope[stride * j].  -> false (for every lane) when a
+// doubling divides by zero; sh.a / b / c are scratch
+__device__ __forceinline__ bool wg_doubling_steps(EcShared &sh, const Fp &px, const Fp &py, Fp *cx, Fp *cy, Fp *cslope, u64 stride) {
+    const u32 t = threadIdx.x;
+    if (t == 0) {
+        EcJac d;
+        d.X = px; d.Y = py; d.Z = fp_one();
+#pragma unroll 1
+        for (u32 j = 0; j < EC_STEPS; ++j) {
+            sh.a[j] = d.X; sh.b[j] = d.Y; sh.c[j] = d.Z;
+            if (j + 1 < EC_STEPS) d = ec_jac_double(d);
+        }
+    }
+    __syncthreads();
+    for (u32 j = t; j < EC_STEPS; j += EC_LANES)
+        if (fp_is_zero(sh.b[j]) || fp_is_zero(sh.c[j])) sh.divisor = 1;              // (Z_{j+1} = 2 Y_j Z_j: a zero y shows in every later Z too)
+    __syncthreads();
+    if (sh.divisor) return false;
+#pragma unroll 1
+    for (u32 j = t; j < EC_STEPS; j += EC_LANES) {
+        const Fp X = sh.a[j], Y = sh.b[j], Z = sh.c[j];
+        const Fp y2 = fp_dbl(Y), zz = fp_sqr(Z);
+        const Fp inv = fp_inv_safegcd(fp_mul(y2, Z));
+        const Fp zi = fp_mul(y2, inv), zi2 = fp_sqr(zi);
+        const Fp x = fp_mul(X, zi2), y = fp_mul(Y, fp_mul(zi2, zi));
+        const Fp xx = fp_sqr(x);
+        store_fp(&cx[stride * j], x); store_fp(&cy[stride * j], y);
+        store_fp(&cslope[stride * j], fp_mul(fp_add(fp_add(fp_dbl(xx), xx), fp_one()), fp_mul(fp_sqr(zz), inv)));
+    }
+    __syncthreads();
+    return true;
+}
+// the highest set bit below position `limit` (<= 256) of x; -1: none
+__device__ __forceinline__ int ec_last_set_below(const u64 *x /* 4 */, u32 limit) {
+    for (u32 wk = 4; wk-- > 0;) {
+        if (64 * wk >= limit) continue;
+        u64 m = x[wk];
+        if (limit - 64 * wk < 64) m &= (1ull << (limit - 64 * wk)) - 1;
+        if (m) return (int)(64 * wk + 63 - (u32)__clzll((long long)m));
+    }
+    return -1;
+}
+// step j of a multiply-add chain: the partial sum before the step, x >> j, the chord's slope (zero where bit j is clear),
+// 1 / (partial.x - point.x)
+struct EcMadStep { Fp x, y, suffix, slope, x_diff_inv; };
+// partial_j = start + the point_i of the set bits i < j of x, point_i = 2^min(i, max_doublings) point = (qx, qy)[qstride * min(i,
+// max_doublings)]: the cells wg_doubling_steps has written.  emit(j, step) takes each of the 256 steps, on the lane that made it.
+// -> false (for every lane) when a partial sum meets its step's point, before anything is emitted; sh.a / b / c are scratch
+template <class Emit>
+__device__ __forceinline__ bool wg_ec_mad_steps(EcShared &sh, const u64 *x /* 4 */, const Fp *qx, const Fp *qy, u64 qstride, const Fp &start_x, const Fp &start_y,
+                                                u32 max_doublings, const Emit &emit) {
+    const u32 t = threadIdx.x;
+    if (t == 0) {
+        EcJac s;
+        s.X = start_x; s.Y = start_y; s.Z = fp_one();
+        for (u32 wi = 0; wi < 4; ++wi) {
+            u64 bits = x[wi];
+#pragma unroll 1
+            while (bits) {
+                const u64 low = bits & (~bits + 1);
+                bits ^= low;
+                const u32 i = 64 * wi + 63 - (u32)__clzll((long long)low), pi = i < max_doublings ? i : max_doublings;
+                const Fp zz = fp_sqr(s.Z);
+                const Fp h = fp_sub(fp_mul(load_fp(&qx[qstride * pi]), zz), s.X), r = fp_sub(fp_mul(load_fp(&qy[qstride * pi]), fp_mul(s.Z, zz)), s.Y);
+                if (fp_is_zero(h)) { sh.meets = 1; bits = 0; wi = 4; continue; }        // the chain ends here: what comes after has no sum to start from
+                const Fp hh = fp_sqr(h), hhh = fp_mul(h, hh), v = fp_mul(s.X, hh);
+                const Fp x3 = fp_sub(fp_sub(fp_sqr(r), hhh), fp_dbl(v));
+                s.Y = fp_sub(fp_mul(r, fp_sub(v, x3)), fp_mul(s.Y, hhh));
+                s.X = x3;
+                s.Z = fp_mul(s.Z, h);
+                sh.a[i] = s.X; sh.b[i] = s.Y; sh.c[i] = s.Z;
+            }
+        }
+    }
+    __syncthreads();
+    if (sh.meets) return false;
+    for (u32 pass = 0; pass < 2; ++pass) {                           // every step's difference is looked at before any step is emitted
+#pragma unroll 1
+        for (u32 j = t; j < EC_STEPS; j += EC_LANES) {
+            const int before = ec_last_set_below(x, j);
+            const Fp X = before < 0 ? start_x : sh.a[before], Z = before < 0 ? fp_one() : sh.c[before];
+            const u32 pi = j < max_doublings ? j : max_doublings;
+            const Fp zz = fp_sqr(Z);
+            const Fp h = fp_sub(fp_mul(load_fp(&qx[qstride * pi]), zz), X);            // = (point.x - partial.x) Z^2
+            if (pass == 0) { if (fp_is_zero(h)) sh.meets = 1; continue; }
+            const Fp Y = before < 0 ? start_y : sh.b[before];
+            const Fp inv = fp_inv_safegcd(fp_mul(h, Z));
+            const Fp zi = fp_mul(h, inv), zi2 = fp_sqr(zi);
+            EcMadStep st;
+            st.x = fp_mul(X, zi2); st.y = fp_mul(Y, fp_mul(zi2, zi));
+            st.x_diff_inv = fp_neg(fp_mul(fp_mul(zz, Z), inv));
+            const bool set = (x[j >> 6] >> (j & 63)) & 1;
+            st.slope = set ? fp_mul(fp_sub(st.y, load_fp(&qy[qstride * pi])), st.x_diff_inv) : fp_zero();
+            u64 sfx[4];                                              // x >> j
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) {
+                const u32 w = k + (j >> 6), sft = j & 63;
+                u64 v = w < 4 ? x[w] >> sft : 0;
+                if (sft && w + 1 < 4) v |= x[w + 1] << (64 - sft);
+                sfx[k] = v;
+            }
+            st.suffix = fp_to_mont(fp_of_words(sfx));
+            emit(j, st);
+        }
+        __syncthreads();
+        if (sh.meets) return false;
+    }
+    return true;
+}
+__global__ __launch_bounds__(EC_LANES) void trace_ec_op_kernel(ColPtrs cols, TraceEcOpLayout L, const u64 *__restrict__ inst, u64 n_blocks, u64 block_rows,
+                                                               u64 addr_begin, u32 *__restrict__ pool_addr, u32 *status) {
+    __shared__ EcShared sh;
+    const u32 t = threadIdx.x;
+    if (t < 21) sh.rec[t] = inst[21 * (u64)blockIdx.x + t];
+    if (t == 0) sh.divisor = sh.meets = 0;
+    __syncthreads();
+    const u64 *rec = sh.rec;
+    const u64 index = rec[0];
+    if (index >= n_blocks || ((rec[4] | rec[8] | rec[12] | rec[16] | rec[20]) >> 60)) {          // (the whole workgroup leaves)
+        if (t == 0) status_error(status, TRACE_ERR_EC_OP_INSTANCE, blockIdx.x);
+        return;
+    }
+    const u64 base = index * block_rows, stride = L.row_stride;
+    Fp *const col = (Fp *)cols.dst[L.col] + base;
+    const u64 *m = rec + 17;
+    if (!wg_doubling_steps(sh, fp_to_mont(fp_of_words(rec + 9)), fp_to_mont(fp_of_words(rec + 13)), col + L.off_dbl_x, col + L.off_dbl_y, col + L.off_dbl_slope, stride)) {
+        if (t == 0) status_error(status, TRACE_ERR_EC_OP_DIVISOR, index);
+        return;
+    }
+    Fp *const pool = (Fp *)cols.dst[L.col_pool];
+    const u64 addr0 = addr_begin + 7 * index;
+    const bool done = wg_ec_mad_steps(sh, m, col + L.off_dbl_x, col + L.off_dbl_y, stride, fp_to_mont(fp_of_words(rec + 1)), fp_to_mont(fp_of_words(rec + 5)), EC_STEPS - 1,
+                                      [&](u32 j, const EcMadStep &st) {
+        const u64 row = stride * j;
+        store_fp(&col[L.off_sum_x + row], st.x); store_fp(&col[L.off_sum_y + row], st.y); store_fp(&col[L.off_suffix + row], st.suffix);
+        if (j != EC_STEPS - 1) { store_fp(&col[L.off_slope + row], st.slope); store_fp(&col[L.off_x_diff_inv + row], st.x_diff_inv); }
+        else {                                                       // R: the sum before step 255 (bit 255 of m is never set)
+            ped_pool_pair(pool, pool_addr, base + L.off_pair[5], addr0 + 5, st.x);
+            ped_pool_pair(pool, pool_addr, base + L.off_pair[6], addr0 + 6, st.y);
+        }
+    });
+    if (!done) {
+        if (t == 0) status_error(status, TRACE_ERR_EC_OP_MEETS, index);
+        return;
+    }
+    // the flag cells (none of them a step's cell) and the pool's other pairs
+    if (t == 0) {
+        const u64 top = m[3];                                        // bits 192 ..: bit 251 = 59, 196 = 4, 192 = 0
+        const bool f2 = ((top >> 59) & 1) && ((top >> 4) & 1), f3 = f2 && (top & 1);
+        store_fp(&col[L.off_flag2], fp_from_u64(f2));
+        store_fp(&col[L.off_flag3], fp_from_u64(f3));
+    }
+    if (t >= 1 && t <= 5) {
+        const u32 k = t - 1;
+        const u32 off = k == 0 ? L.off_pair[0] : k == 1 ? L.off_pair[1] : k == 2 ? L.off_pair[2] : k == 3 ? L.off_pair[3] : L.off_pair[4];      // (selects: no lane-indexed kernel argument)
+        ped_pool_pair(pool, pool_addr, base + off, addr0 + k, fp_to_mont(fp_of_words(rec + 1 + 4 * k)));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ range-check builtin and pool
 // the pool's padding values in order (utils.rs:357-380 RangeCheckPool::get_ordered_values_with_padding's second half), then rc_hi
 __device__ __forceinline__ u32 rc_padding(const TraceRcPlan &p, const uint16_t *padding, u64 j) { return j < p.n_padding ? padding[j] : p.rc_hi; }
@@ -779,6 +971,12 @@ hipError_t launch_trace_poseidon(hipStream_t st, const ColPtrs &cols, const Trac
     if (!n_given) return hipSuccess;
     hipLaunchKernelGGL(trace_poseidon_kernel, grid_for(n_given, 64), dim3(64), 0, st, cols, L, d_round_keys, d_instances, n_given, n_blocks, block_rows, addr_begin,
                        d_pool_addr, d_status);
+    return hipGetLastError();
+}
+hipError_t launch_trace_ec_op(hipStream_t st, const ColPtrs &cols, const TraceEcOpLayout &L, const u64 *d_instances, u64 n_given, u64 n_blocks, u64 block_rows,
+                              u64 addr_begin, u32 *d_pool_addr, u32 *d_status) {
+    if (!n_given) return hipSuccess;
+    hipLaunchKernelGGL(trace_ec_op_kernel, dim3((u32)n_given), dim3(EC_LANES), 0, st, cols, L, d_instances, n_blocks, block_rows, addr_begin, d_pool_addr, d_status);
     return hipGetLastError();
 }
 hipError_t launch_trace_rc_builtin(hipStream_t st, const TraceRcPlan &p, const u64 *d_given, const uint16_t *d_padding, Fp *rc, Fp *npc, u32 *d_pool_addr) {

@@ -144,3 +144,29 @@ def seeded_poseidon_instances(slots, seed=SEED0):
     """`slots` distinct Poseidon instances (index, in0, in1, in2), one per slot, as air-private-input.json's `poseidon` rows: inputs
     < 2^251 from SplitMix64 (see seeded_bitwise_instances)"""
     return _seeded_values(slots, 3, seed ^ 0x504f53)
+
+
+def ec_op_slots(log_steps):
+    """EC-op builtin instances a 2^log_steps-step starknet trace has room for (the recursive layout has no EC-op builtin)"""
+    from sandstorm_amd.layouts import starknet as sk
+    return (1 << log_steps) // sk.EC_OP_BUILTIN_RATIO
+
+
+def seeded_ec_op_instances(slots, seed=SEED0):
+    """`slots` distinct EC-op instances (index, p_x, p_y, q_x, q_y, m), one per slot, as air-private-input.json's `ec_op` rows: P and Q
+    are 2 * slots consecutive points of the walk k G, (k + 1) G, ... from a seeded k (one scalar multiplication, then one affine
+    addition of G per point: the Python mirror's arithmetic, layouts/starknet.py), m < 2^251 from SplitMix64.  No two of the points
+    share an x, so every instance is distinct and no P meets its Q; that no partial sum meets a doubling of Q on the way is left to
+    the generators, which refuse such an instance (none of the seeds the suite and the tools use has one)"""
+    from sandstorm_amd.layouts import starknet as sk
+    raw = splitmix64_stream(seed ^ 0x45434f50, 4 * (slots + 1)).reshape(slots + 1, 4).copy()
+    raw[:, 3] &= np.uint64((1 << 59) - 1)
+    word = lambda r: sum(int(r[j]) << (64 * j) for j in range(4))
+    point = sk._ec_mul(word(raw[slots]) | 1 << 200, sk.GENERATOR)
+    rows = []
+    for i in range(slots):
+        p = point
+        q = sk._ec_add(p, sk.GENERATOR)
+        point = sk._ec_add(q, sk.GENERATOR)
+        rows.append((i, p[0], p[1], q[0], q[1], word(raw[i])))
+    return rows

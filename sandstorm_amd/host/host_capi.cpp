@@ -621,15 +621,16 @@ int ssh_trace_last_stats(uint64_t out[4]) {
     out[0] = s.bytes_uploaded; out[1] = s.pedersen_on_host; out[2] = s.pedersen_on_device; out[3] = s.templates_uploaded;
     return 0;
 }
-// the same with the buffer's length (ssh_trace_last_stats keeps its four words: its callers pass four): the first min(n_words, 8) of
+// the same with the buffer's length (ssh_trace_last_stats keeps its four words: its callers pass four): the first min(n_words, 10) of
 // the four words above, then the given bitwise instances traced through a template on the host / on the device from their inputs
-// (ss_trace_bitwise), then the same two for the Poseidon builtin (ss_trace_poseidon); words beyond the eighth are zeroed
+// (ss_trace_bitwise), then the same two for the Poseidon builtin (ss_trace_poseidon) and for the EC-op builtin (ss_trace_ec_op); words
+// beyond the tenth are zeroed
 int ssh_trace_last_stats_n(uint64_t *out, uint64_t n_words) {
     if (!out) { g_err = "ssh_trace_last_stats_n: NULL argument"; return 1; }
     const tracedetail::DeviceTraceStats &s = tracedetail::device_trace_stats();
-    const uint64_t all[8] = {s.bytes_uploaded, s.pedersen_on_host, s.pedersen_on_device, s.templates_uploaded, s.bitwise_on_host, s.bitwise_on_device,
-                             s.poseidon_on_host, s.poseidon_on_device};
-    for (uint64_t k = 0; k < n_words; ++k) out[k] = k < 8 ? all[k] : 0;
+    const uint64_t all[10] = {s.bytes_uploaded, s.pedersen_on_host, s.pedersen_on_device, s.templates_uploaded, s.bitwise_on_host, s.bitwise_on_device,
+                              s.poseidon_on_host, s.poseidon_on_device, s.ec_op_on_host, s.ec_op_on_device};
+    for (uint64_t k = 0; k < n_words; ++k) out[k] = k < 10 ? all[k] : 0;
     return 0;
 }
 

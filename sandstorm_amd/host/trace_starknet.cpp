@@ -497,9 +497,10 @@ struct HostBackend {
     void pedersen_done() { done({COL_PEDERSEN_X, COL_PEDERSEN_Y, COL_PEDERSEN_SUFFIX, COL_PEDERSEN_SLOPE}); }
     static constexpr bool pedersen_on_device = false;      // every block's instance goes through builtin()
     void pedersen_given(const std::vector<PedersenInstance> &, uint64_t, uint64_t, uint64_t) {}
-    static constexpr bool bitwise_on_device = false, poseidon_on_device = false;
+    static constexpr bool bitwise_on_device = false, poseidon_on_device = false, ec_op_on_device = false;
     void bitwise_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
     void poseidon_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
+    void ec_op_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
 };
 
 // ---- the device backend: the same sections as uploads of plans / templates and kernel launches (device_trace.hpp, csrc/trace.hip)
@@ -552,6 +553,19 @@ struct DeviceBackend {
         l.col_pool = COL_NPC;
         for (int k = 0; k < 6; ++k) l.off_pair[k] = (uint32_t)NPC_POSEIDON_ADDRS[k];
         dt.poseidon(dev, l, poseidon_round_keys().data()->data(), step, begin, host_traced);
+    }
+    // and the given EC-op instances: ss_trace_ec_op makes the cells the section's `place` lambda names
+    static constexpr bool ec_op_on_device = true;
+    void ec_op_given(DeviceInstances &dev, uint64_t step, uint64_t begin, uint64_t host_traced) {
+        ss_trace_ec_op_layout l{};
+        l.col = COL_AUXILIARY; l.row_stride = 64;
+        l.off_dbl_x = OP_Q_DOUBLING_X; l.off_dbl_y = OP_Q_DOUBLING_Y; l.off_dbl_slope = OP_Q_DOUBLING_SLOPE;
+        l.off_sum_x = OP_R_PARTIAL_SUM_X; l.off_sum_y = OP_R_PARTIAL_SUM_Y; l.off_suffix = OP_M_SUFFIX;
+        l.off_slope = OP_R_PARTIAL_SUM_SLOPE; l.off_x_diff_inv = OP_R_PARTIAL_SUM_X_DIFF_INV;
+        l.off_flag2 = OP_M_BIT251_AND_BIT196; l.off_flag3 = OP_M_BIT251_AND_BIT196_AND_BIT192;
+        l.col_pool = COL_NPC;
+        for (int k = 0; k < 7; ++k) l.off_pair[k] = (uint32_t)NPC_EC_OP_ADDRS[k];
+        dt.ec_op(dev, l, step, begin, host_traced);
     }
 };
 
@@ -714,9 +728,13 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
         const auto given = instances_by_index(priv.ec_op, n / step, "ec_op");
         // gen_dummy_instance (ec_op/mod.rs:84-96): P0 + 1 * G
         const U256x5 dummy{canonical_of(cv.shift.x), canonical_of(cv.shift.y), canonical_of(cv.generator.x), canonical_of(cv.generator.y), U256{1, 0, 0, 0}};
+        // the device makes the given instances' cells from P, Q, m (ec_op_given below) and takes the dummy instance as its one template
+        DeviceInstances dev = device_instances(Backend::ec_op_on_device, priv.ec_op, n / step, 5, [](const EcOpInstance &e, unsigned k) -> const U256 & {
+            return k == 0 ? e.p_x : k == 1 ? e.p_y : k == 2 ? e.q_x : k == 3 ? e.q_y : e.m;
+        });
         Instances<U256x5, EcOpTrace> inst;
         inst.assign(n / step, [&](uint64_t i) {
-            auto it = given.find((uint32_t)i);
+            auto it = dev.holds(i) ? given.end() : given.find((uint32_t)i);
             return it != given.end() ? U256x5{it->second->p_x, it->second->p_y, it->second->q_x, it->second->q_y, it->second->m} : dummy;
         });
         auto trace_of = [](const U256x5 &in5) {              // (a scalar multiplication with its doubling chain per instance)
@@ -753,6 +771,7 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
             const Felt values[7] = {t.p.x, t.p.y, t.q.x, t.q.y, t.m, t.r.x, t.r.y};
             for (int k = 0; k < 7; ++k) s.pair(NPC_EC_OP_ADDRS[k], k, values[k]);
         });
+        be.ec_op_given(dev, step, pi.segments[7].begin_addr, (uint64_t)std::count_if(inst.keys.begin(), inst.keys.end(), [&](const U256x5 &k) { return k != dummy; }));
     }
     // ---- Poseidon (trace.rs:779-888)
     {

@@ -690,15 +690,15 @@ def device_base_trace(ctx, layout, trace_bin: bytes, memory_bin: bytes, pi, priv
 
 
 TRACE_STATS_KEYS = ("bytes_uploaded", "pedersen_on_host", "pedersen_on_device", "templates_uploaded", "bitwise_on_host", "bitwise_on_device", "poseidon_on_host",
-                    "poseidon_on_device")
+                    "poseidon_on_device", "ec_op_on_host", "ec_op_on_device")
 
 
 def trace_last_stats():
     """what the last device generation on this thread (device_base_trace, prove_files_device) moved (host_capi.cpp ssh_trace_last_stats_n)
     -> {"bytes_uploaded", "pedersen_on_host", "pedersen_on_device", "templates_uploaded"}: the generator's uploads in bytes, the given
     Pedersen instances whose curve steps ran on the host / on the device, the builtin templates uploaded (all builtins); and
-    {"bitwise_on_host", "bitwise_on_device", "poseidon_on_host", "poseidon_on_device"}: the given bitwise / Poseidon instances that went
-    through a host-made template / were traced on the device from their inputs"""
+    {"bitwise_on_host", "bitwise_on_device", "poseidon_on_host", "poseidon_on_device", "ec_op_on_host", "ec_op_on_device"}: the given
+    bitwise / Poseidon / EC-op instances that went through a host-made template / were traced on the device from their inputs"""
     out = (C.c_uint64 * len(TRACE_STATS_KEYS))()
     fn = load().ssh_trace_last_stats_n
     fn.argtypes = [C.POINTER(C.c_uint64), C.c_uint64]

@@ -3,12 +3,13 @@
   prove      the proof alone on the resident columns (ssh_prove)
   total      ONE ssh_prove_files_device call from the files to the proof
 and, with E2E_HOST=1, the host-generated path (ssh_prove_files: generator thread + overlapped uploads) beside it.
-python tools/e2e_device.py [starknet recursive] [log_steps] [--saturate-pedersen] [--saturate-bitwise] [--saturate-poseidon] [--packed] [--json FILE]; one
+python tools/e2e_device.py [starknet recursive] [log_steps] [--saturate-pedersen] [--saturate-bitwise] [--saturate-poseidon] [--saturate-ec-op] [--packed] [--json FILE]; one
 line per layout, flushed as it is known.
 --saturate-pedersen: every Pedersen slot of the statement holds a distinct seeded instance (examples.seeded_pedersen_instances: 32768 of
 them in the starknet layout at 2^20 steps) instead of the dummy one - the normal case of a real run, and the generator's worst.
 --saturate-bitwise, --saturate-poseidon: the same for the bitwise builtin's slots (examples.seeded_bitwise_instances: 16384 in the starknet layout
 at 2^20 steps, 131072 in the recursive one) and the Poseidon builtin's (examples.seeded_poseidon_instances: 32768, starknet only); they combine.
+--saturate-ec-op: the same for the EC-op builtin's slots (examples.seeded_ec_op_instances: 1024, starknet only).
 --packed: those instances handed over as packed uint64 rows (hostlib.pack_instances), converted once outside the timed calls.
 --json FILE: the raw run lists (seconds) per layout, appended as one JSON line.
 To time an EARLIER commit beside this one (profiles/pedersen_device_trace.json), copy this file and sandstorm_amd/examples.py (the seeded
@@ -26,7 +27,7 @@ from sandstorm_amd import backend as be, binary, examples, hostlib, public_input
 from sandstorm_amd.prover import ProofOptions                                       # noqa: E402
 
 
-def main(layouts, log_steps=20, repeats=5, saturate_pedersen=False, json_path=None, packed=False, saturate_bitwise=False, saturate_poseidon=False):
+def main(layouts, log_steps=20, repeats=5, saturate_pedersen=False, json_path=None, packed=False, saturate_bitwise=False, saturate_poseidon=False, saturate_ec_op=False):
     log_n = log_steps + 4
     n = 1 << log_n
     ctx = be.Context(0)
@@ -54,6 +55,8 @@ def main(layouts, log_steps=20, repeats=5, saturate_pedersen=False, json_path=No
             priv["bitwise"] = examples.seeded_bitwise_instances(examples.bitwise_slots(layout, log_steps))
         if saturate_poseidon and layout == "starknet":
             priv["poseidon"] = examples.seeded_poseidon_instances(examples.poseidon_slots(log_steps))
+        if saturate_ec_op and layout == "starknet":
+            priv["ec_op"] = examples.seeded_ec_op_instances(examples.ec_op_slots(log_steps))
         given = {name: len(rows) for name, rows in priv.items()}
         priv = priv or None
         # --packed: the instances converted to the generators' uint64 rows ONCE, outside the timed calls (hostlib.pack_instances), as a
@@ -100,7 +103,7 @@ def main(layouts, log_steps=20, repeats=5, saturate_pedersen=False, json_path=No
         if json_path:
             with open(json_path, "a") as f:
                 f.write(json.dumps({"layout": layout, "log_steps": log_steps, "pedersen_instances": given.get("pedersen", 0), "bitwise_instances": given.get("bitwise", 0),
-                                    "poseidon_instances": given.get("poseidon", 0), "packed": bool(priv) and not any(isinstance(v, list) for v in priv.values()), "gen_s": gen_s,
+                                    "poseidon_instances": given.get("poseidon", 0), "ec_op_instances": given.get("ec_op", 0), "packed": bool(priv) and not any(isinstance(v, list) for v in priv.values()), "gen_s": gen_s,
                                     "prove_s": prove_s, "total_s": total_s, "trace_gen_s": inner, "last_generation": stats}) + "\n")
         print("%s 2^%d steps%s, %.1f MB of files: device generator %s s; proof alone %s s; files -> proof (device generator) %s s = %.3f x the proof "
               "(the columns final %s s into the call); last generation %s"
@@ -120,4 +123,4 @@ if __name__ == "__main__":
     steps = [int(a) for a in sys.argv[1:] if a.isdigit()]
     json_out = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
     main(names, steps[0] if steps else 20, saturate_pedersen="--saturate-pedersen" in sys.argv, json_path=json_out, packed="--packed" in sys.argv,
-         saturate_bitwise="--saturate-bitwise" in sys.argv, saturate_poseidon="--saturate-poseidon" in sys.argv)
+         saturate_bitwise="--saturate-bitwise" in sys.argv, saturate_poseidon="--saturate-poseidon" in sys.argv, saturate_ec_op="--saturate-ec-op" in sys.argv)

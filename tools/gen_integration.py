@@ -15,7 +15,8 @@ SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int": "c_int"
            "char": "c_char", "double": "f64", "float": "f32", "ss_status": "c_int", "ss_ctx": "SsCtx", "ss_comm": "SsComm", "ss_air_program": "SsAirProgram",
            "ss_perm_operand": "SsPermOperand", "ss_gather_job": "SsGatherJob", "uint16_t": "u16", "ss_trace_layout": "SsTraceLayout",
            "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan", "ss_trace_pedersen_layout": "SsTracePedersenLayout",
-           "ss_trace_bitwise_layout": "SsTraceBitwiseLayout", "ss_trace_poseidon_layout": "SsTracePoseidonLayout"}
+           "ss_trace_bitwise_layout": "SsTraceBitwiseLayout", "ss_trace_poseidon_layout": "SsTracePoseidonLayout",
+           "ss_trace_ec_op_layout": "SsTraceEcOpLayout"}
 
 
 def prototypes(text=None):
@@ -94,6 +95,9 @@ def rust_block():
              "    pub col_full: u32, pub full_stride: u32, pub off_full: [u32; 3], pub off_full_sq: [u32; 3],",
              "    pub col_partial: u32, pub partial_stride: u32, pub off_partial: u32, pub off_partial_sq: u32, pub n_partial: u32,",
              "    pub col_tail: u32, pub tail_stride: u32, pub off_tail: u32, pub off_tail_sq: u32, pub tail_first: u32, pub col_pool: u32, pub off_pair: [u32; 6],", "}",
+             "#[repr(C)] pub struct SsTraceEcOpLayout {     // ss_trace_ec_op_layout",
+             "    pub col: u32, pub row_stride: u32, pub off_dbl_x: u32, pub off_dbl_y: u32, pub off_dbl_slope: u32, pub off_sum_x: u32, pub off_sum_y: u32, pub off_suffix: u32,",
+             "    pub off_slope: u32, pub off_x_diff_inv: u32, pub off_flag2: u32, pub off_flag3: u32, pub col_pool: u32, pub off_pair: [u32; 7],", "}",
              "#[link(name = \"sandstorm_hip\")]", "extern \"C\" {"]
     for name, ret, params in prototypes():
         args = ", ".join("%s: %s" % (p if p not in ("in", "type", "ref", "mod") else p + "_", rust_type(t)) for t, p in params)
