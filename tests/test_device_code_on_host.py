@@ -91,9 +91,11 @@ def test_the_base_trace_made_by_the_device_code(emulated_library):
     """tests/test_gpu_device_trace.py: csrc/trace.hip (one lane per Cairo cycle, builtin templates, the pools and the ordered memory by
     histogram + prefix sum + binary search) against the host generator, cell for cell - the reference's example run with and without
     real builtin instances, the bench's statements of both layouts, the reference's bootloader run with every builtin, the input's
-    errors - and the 2^14-step files -> proof call through it (the committed proof's bytes)"""
-    out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_device_trace.py"])
-    assert "6 passed, 3 skipped" in out, out[-500:]
+    errors -, tests/test_gpu_trace_kernels.py: every ss_trace_* entry point of the base trace alone against Python integers - every
+    instruction form, every input-error bit, the ordered memory's table collisions, scan chunks and gap bookkeeping - and the 2^14-step
+    files -> proof call through it (the committed proof's bytes)"""
+    out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_device_trace.py", "tests/test_gpu_trace_kernels.py"])
+    assert "86 passed, 3 skipped" in out, out[-500:]          # 8 whole generations (3 at hardware sizes skipped) + 78 calls of single entry points
     heavy()
     out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_recursive_claim.py", "-k", "device_generator and 14"], timeout=2400)
     assert "1 passed" in out, out[-500:]

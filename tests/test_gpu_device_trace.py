@@ -93,6 +93,22 @@ def test_columns_of_the_bench_statements(ctx, layout, log_steps):
     assert_same_columns(got, want)
 
 
+@pytest.mark.parametrize("layout,log_steps", [("recursive", 14), ("starknet", 17)])
+def test_columns_of_the_synthetic_run(ctx, layout, log_steps):
+    """tests/cairo_machine.py's run - fourteen workgroups of busy cycles: 252-bit products, sums with immediates near p, conditional jumps
+    on values above 2^250 (the kernel's inversions), call / ret, jmp abs, ap += res over untouched addresses (gap fillers), an operand
+    through [op0] - as a statement of each layout at the smallest size this file uses for it"""
+    import cairo_machine
+    from sandstorm_amd import binary, hostlib
+    states, memory, pi = cairo_machine.synthetic_run(layout, log_steps)
+    assert cairo_machine.busy_cycles(states) > 8 * 128
+    trace_bin, memory_bin = binary.write_register_states(states), binary.write_memory(memory)
+    gen = hostlib.starknet_base_trace if layout == "starknet" else hostlib.recursive_base_trace
+    want = gen(trace_bin, memory_bin, pi)
+    got = device_columns(ctx, layout, trace_bin, memory_bin, pi, None)
+    assert_same_columns(got, want)
+
+
 def test_starknet_columns_of_the_references_bootloader_run_with_every_builtin(ctx):
     """the reference's own starknet-layout run (example/bootloader: 2^17 steps, two real Pedersen instances) with real range-check,
     ECDSA, bitwise, EC-op and Poseidon instances on top: a template per distinct instance, the dummies' beside"""

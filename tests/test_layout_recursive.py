@@ -10,6 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EX = os.path.join(ROOT, "tests", "golden", "example")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))          # tests/cairo_machine.py
 
 
 from sandstorm_amd.examples import load_run, recursive_example  # noqa: E402,F401  (moved: bench.py proves these statements too)
@@ -307,6 +308,27 @@ def test_cpp_base_trace_equals_the_python_one(oracle):
     from sandstorm_amd._lib import SandstormHipError
     with pytest.raises(SandstormHipError, match="power of two"):
         hostlib.recursive_base_trace(trace_bin[:24 * 1000], memory_bin, pi)
+
+
+def test_cpp_base_trace_equals_the_python_one_on_the_synthetic_run(oracle):
+    """the same on tests/cairo_machine.py's run at 2^14 steps - ~1 850 busy cycles of 252-bit products, sums with immediates near p,
+    conditional jumps on values up to the last step below p, call / ret, jmp abs, ap += res over 40 untouched addresses, an operand through
+    [op0] - where the example run has 34 busy cycles and no product: a disagreement on a multiply or on a jump taken with a large dst would
+    otherwise be shared by the host generator and the device code held to it"""
+    import numpy as np
+    import cairo_machine
+    from sandstorm_amd import binary, hostlib
+    from sandstorm_amd.layouts import recursive as rec
+    states, memory, pi = cairo_machine.synthetic_run("recursive", 14)
+    assert cairo_machine.busy_cycles(states) > 8 * 128
+    jumps = [memory[w.dst_addr(st.ap, st.fp)] for st in states[:cairo_machine.busy_cycles(states)] for w in [binary.Word(memory[st.pc])] if w.pc_update == 4]
+    assert sum(1 for d in jumps if d > 2**250) > 256 and jumps.count(0) == 2 and 1 in jumps
+    assert sum(1 for a in range(1, len(memory)) if memory[a] is None) >= 40           # the gap fillers' work
+    want = rec.base_trace(states, memory, pi)
+    got = hostlib.recursive_base_trace(binary.write_register_states(states), binary.write_memory(memory), pi)
+    assert len(got) == len(want) == 7
+    for c, (g, w) in enumerate(zip(got, want)):
+        assert np.array_equal(g, oracle.to_mont(w)), "column %d" % c
 
 
 def test_cpp_trace_refuses_a_far_away_address_without_sizing_anything_by_it():
