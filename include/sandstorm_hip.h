@@ -517,7 +517,11 @@ enum { SS_TRACE_ERR_MISSING_CELL = 1,        /* the run reads a cell memory.bin 
        SS_TRACE_ERR_POSEIDON_INSTANCE = 65536, /* ss_trace_poseidon: the same, for a Poseidon instance                  */
        SS_TRACE_ERR_EC_OP_INSTANCE = 131072, /* ss_trace_ec_op: the same, for an EC-op instance                        */
        SS_TRACE_ERR_EC_OP_DIVISOR = 262144,  /* ss_trace_ec_op: a doubling of Q whose y is zero (the tangent's slope divides by it) */
-       SS_TRACE_ERR_EC_OP_MEETS = 524288 };  /* ss_trace_ec_op: a partial sum shares its x with its step's point (see there) */
+       SS_TRACE_ERR_EC_OP_MEETS = 524288,    /* ss_trace_ec_op: a partial sum shares its x with its step's point (see there) */
+       SS_TRACE_ERR_ECDSA_INSTANCE = 1 << 20, /* ss_trace_ecdsa: an instance's index is beyond the blocks, or an input has a bit from 252 up: skipped */
+       SS_TRACE_ERR_ECDSA_INVALID = 1 << 21,  /* ss_trace_ecdsa: neither root of the key verifies the signature, or a scalar is zero or has bit 251 set */
+       SS_TRACE_ERR_ECDSA_DIVISOR = 1 << 22,  /* ss_trace_ecdsa: a doubling whose y is zero, or a chord between points that share their x   */
+       SS_TRACE_ERR_ECDSA_MEETS = 1 << 23 };  /* ss_trace_ecdsa: a partial sum meets its step's point above the scalar's highest set bit (see there) */
 /* memory.bin on the device: d_records = the file's bytes (n_records x (u64 address, 32-byte little-endian word), uploaded by
  * the caller) -> d_image[address] as 4 x u64; cells the file does not name are marked (all-ones: not a field element).
  * cells: entries of d_image; records beyond it are dropped (no address above n / 2 can be accessed by a valid run). */
@@ -648,6 +652,54 @@ typedef struct {
 ss_status ss_trace_ec_op(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_ec_op_layout *layout,
                          const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr,
                          uint32_t *d_status);
+/* A GIVEN ECDSA instance's cells from the public key, the message and the signature, computed on the device
+ * (builtins/src/ecdsa/mod.rs:85-147 InstanceTrace::new, 157-206 the chains, 275-304 verify and mimic_ec_mad_air; starknet trace.rs:428-523)
+ * - no template, 168 bytes per instance.  d_instances: n_given records of 21 u64 = index, key.x[4], key.y[4], message[4], r[4], w[4]
+ * (canonical little-endian limbs below 2^252); key.y is EITHER square root of x^3 + x + beta (the caller's: the device takes no roots) and
+ * the kernel orders the two candidates y, p - y itself, the canonically larger first, as `verify` does.  instance `index` owns rows
+ * [index * block_rows, (index + 1) * block_rows) of the columns (col_rows felts each; n_blocks * block_rows <= col_rows).  d_points: 252
+ * affine points as Montgomery felts (x, y) - entries 0 .. 250 the 2^i G, entry 251 the shift point P0 (the caller's: the library derives
+ * no constants of its own).  All cells are in column `col`:
+ *   the generator's chain z G from -P0 (point i = d_points[min(i, 250)]): for each of the 256 steps j, row off_gen_* + gen_stride * j gets
+ *     the partial sum before the step (off_gen_x, off_gen_y), the chord's slope (off_gen_slope; zero where bit j is clear),
+ *     1 / (partial.x - point.x) (off_gen_x_diff_inv) and message >> j (off_gen_suffix);
+ *   half 0, the key's: for each step j, row off_* + row_stride * j gets the doubling point 2^j Q (off_dbl_x, off_dbl_y) with its tangent's
+ *     slope (off_dbl_slope) and, of the chain r Q from P0, the partial sum (off_sum_x, off_sum_y), the slope (off_slope), the x-difference's
+ *     inverse (off_x_diff_inv) and r >> j (off_suffix);
+ *   half 1, B = z G + r Q: the same cells 256 * row_stride rows further down, for B's doublings and the chain w B from P0;
+ *   then - last, as four of them are step-255 cells of the chains in the starknet layout - the slope of the chord through w B and -P0
+ *     (off_r_point_slope) and 1 / (w B.x - P0.x) (off_r_point_x_diff_inv), 1 / r, 1 / w, 1 / message in the field (off_r_inv, off_w_inv,
+ *     off_message_inv), key.x^2 (off_pubkey_x_squared), the slope of the chord through z G and r Q (off_b_slope) and 1 / (z G.x - r Q.x)
+ *     (off_b_x_diff_inv);
+ * and the two memory-pool pairs (addr_begin + 2 * index + k, value) of key.x and the message at rows off_pair[k] (even) of col_pool, their
+ * integer addresses in d_pool_addr[row / 2] (col_rows / 2 u32).  All values Montgomery felts, bit-identical to the host generator's.  No
+ * cell of the columns ever holds an intermediate value of another kind: the chains' scratch is LDS, the doubling points are read back from
+ * their own cells.  The candidate Q = (x, root) is accepted when x(w B - P0) = r; a candidate that fails, or whose partial sum meets its
+ * step's point at a step up to the scalar's highest set bit (where mimic_ec_mad_air gives up), is rejected and the other root runs the same
+ * way over the same cells: a full second pass that writes every cell of the first again.
+ * Call it AFTER ss_trace_builtin has laid the dummy signature's template over all blocks and BEFORE ss_trace_ec_op (the EC-op section
+ * leaves its step-255 slope cells to this one).  The indices must be distinct.
+ * Refused with an error (nothing launched): NULL pointers (also with n_given = 0), blocks that do not fit the columns, a column >= ncols,
+ * a cell that leaves its block (2 * 256 steps at row_stride, 256 at gen_stride), an odd pool offset, n_given > n_blocks.  Found on the
+ * device, as bits of d_status: an index >= n_blocks or an input with a bit from 252 up - skipped, nothing written
+ * (SS_TRACE_ERR_ECDSA_INSTANCE); message, r or w zero or with bit 251 set - no chain is run -, or both roots rejected
+ * (SS_TRACE_ERR_ECDSA_INVALID: the host generator's "signature is invalid"; a key.y that is no root of the curve's equation ends here or at
+ * the next); a doubling whose y is zero - key.y = 0 is one -, or a zero z G.x - r Q.x or w B.x - P0.x (SS_TRACE_ERR_ECDSA_DIVISOR: "a curve
+ * step divides by zero"); a partial sum that meets its step's point ABOVE the scalar's highest set bit, which mimic_ec_mad_air does not
+ * see and gen_ec_mad_steps divides by (SS_TRACE_ERR_ECDSA_MEETS: "a partial sum meets the fixed point").  The last two end the instance at
+ * the candidate that finds them (the reference would still try the other root); with a key on the curve neither is reachable - the start
+ * points are fixed and the group's order is prime.  After any of the last three the instance's cells are unfinished and the caller must
+ * refuse the generation - host/device_trace.hpp does. */
+typedef struct {
+    uint32_t col, row_stride, gen_stride;                                                 /* 64 and 128 in the starknet layout */
+    uint32_t off_dbl_x, off_dbl_y, off_dbl_slope, off_sum_x, off_sum_y, off_slope, off_x_diff_inv, off_suffix;   /* a half's step j: row off + row_stride * (256 * half + j) */
+    uint32_t off_gen_x, off_gen_y, off_gen_slope, off_gen_x_diff_inv, off_gen_suffix;     /* step j: row off + gen_stride * j */
+    uint32_t off_r_point_slope, off_r_point_x_diff_inv, off_r_inv, off_w_inv, off_message_inv, off_pubkey_x_squared, off_b_slope, off_b_x_diff_inv;
+    uint32_t col_pool, off_pair[2];                                                       /* key.x, message */
+} ss_trace_ecdsa_layout;
+ss_status ss_trace_ecdsa(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_ecdsa_layout *layout,
+                         const uint64_t *d_points, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows,
+                         uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
 /* The 16-bit range-check pool (utils.rs:357-380; starknet trace.rs:142-165, 246-292, 388-426).  The caller counts the pool's
  * values (65536 bins: the instructions' offsets, the builtin's parts) and hands over
  *   d_first[j], j <= rc_hi - rc_lo + 1: ordered values before value rc_lo + j (every value of [rc_lo, rc_hi] max(count, 1) times),

@@ -112,6 +112,8 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p]),
     "ss_trace_ec_op": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                  C.c_void_p]),
+    "ss_trace_ecdsa": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                 C.c_void_p, C.c_void_p]),
     "ss_trace_rc_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "ss_trace_rc_builtin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ss_trace_ordered_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),

@@ -1407,7 +1407,9 @@ static_assert(SS_TRACE_ERR_MISSING_CELL == TRACE_ERR_MISSING_CELL && SS_TRACE_ER
               SS_TRACE_ERR_PEDERSEN_INFINITY == TRACE_ERR_PEDERSEN_INFINITY && SS_TRACE_ERR_PEDERSEN_INSTANCE == TRACE_ERR_PEDERSEN_INSTANCE &&
               SS_TRACE_ERR_BITWISE_INSTANCE == TRACE_ERR_BITWISE_INSTANCE && SS_TRACE_ERR_POSEIDON_INSTANCE == TRACE_ERR_POSEIDON_INSTANCE &&
               SS_TRACE_ERR_EC_OP_INSTANCE == TRACE_ERR_EC_OP_INSTANCE && SS_TRACE_ERR_EC_OP_DIVISOR == TRACE_ERR_EC_OP_DIVISOR &&
-              SS_TRACE_ERR_EC_OP_MEETS == TRACE_ERR_EC_OP_MEETS && SS_TRACE_BITWISE_CELLS == TRACE_BITWISE_CELLS && SS_TRACE_BITWISE_PAIRS == TRACE_BITWISE_PAIRS,
+              SS_TRACE_ERR_EC_OP_MEETS == TRACE_ERR_EC_OP_MEETS && SS_TRACE_ERR_ECDSA_INSTANCE == TRACE_ERR_ECDSA_INSTANCE &&
+              SS_TRACE_ERR_ECDSA_INVALID == TRACE_ERR_ECDSA_INVALID && SS_TRACE_ERR_ECDSA_DIVISOR == TRACE_ERR_ECDSA_DIVISOR &&
+              SS_TRACE_ERR_ECDSA_MEETS == TRACE_ERR_ECDSA_MEETS && SS_TRACE_BITWISE_CELLS == TRACE_BITWISE_CELLS && SS_TRACE_BITWISE_PAIRS == TRACE_BITWISE_PAIRS,
               "the header's constants are the kernels'");
 bool trace_layout_ok(const ss_trace_layout *l) {
     if (!l) return false;
@@ -1494,7 +1496,7 @@ ss_status ss_trace_pedersen(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols
     return SS_OK;
 }
 namespace {
-// what ss_trace_bitwise, ss_trace_poseidon and ss_trace_ec_op ask of their blocks and columns before anything is launched
+// what ss_trace_bitwise, ss_trace_poseidon, ss_trace_ec_op and ss_trace_ecdsa ask of their blocks and columns before anything is launched
 const char *trace_blocks_problem(const ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const void *layout, const uint64_t *d_instances,
                                  uint64_t n_given, uint64_t n_blocks, uint64_t block_rows, const uint32_t *d_pool_addr, const uint32_t *d_status) {
     if (!ctx || !d_cols || !layout || !d_pool_addr || !d_status || (n_given && !d_instances)) return "NULL argument";
@@ -1580,6 +1582,33 @@ ss_status ss_trace_ec_op(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, u
     if (!n_given) return SS_OK;
     ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
     HIP_TRY(launch_trace_ec_op(ctx->stream, cp, L, d_instances, n_given, n_blocks, block_rows, addr_begin, d_pool_addr, d_status));
+    return SS_OK;
+}
+ss_status ss_trace_ecdsa(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const ss_trace_ecdsa_layout *layout,
+                         const uint64_t *d_points, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks, uint64_t block_rows,
+                         uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status) {
+    if (const char *problem = trace_blocks_problem(ctx, d_cols, ncols, col_rows, layout, d_instances, n_given, n_blocks, block_rows, d_pool_addr, d_status))
+        return fail(SS_ERR_INVALID, "%s", problem);
+    if (!d_points) return fail(SS_ERR_INVALID, "NULL argument");
+    static_assert(sizeof(ss_trace_ecdsa_layout) == sizeof(TraceEcdsaLayout), "ss_trace_ecdsa_layout is TraceEcdsaLayout");
+    TraceEcdsaLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (L.col >= ncols || L.col_pool >= ncols) return fail(SS_ERR_INVALID, "a column beyond ncols");
+    if (!L.row_stride || !L.gen_stride) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    const uint64_t span = 511ull * L.row_stride, gen_span = 255ull * L.gen_stride;        // two halves of 256 steps; the generator's 256
+    for (uint32_t off : {L.off_dbl_x, L.off_dbl_y, L.off_dbl_slope, L.off_sum_x, L.off_sum_y, L.off_slope, L.off_x_diff_inv, L.off_suffix})
+        if (off + span >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    for (uint32_t off : {L.off_gen_x, L.off_gen_y, L.off_gen_slope, L.off_gen_x_diff_inv, L.off_gen_suffix})
+        if (off + gen_span >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    for (uint32_t off : {L.off_r_point_slope, L.off_r_point_x_diff_inv, L.off_r_inv, L.off_w_inv, L.off_message_inv, L.off_pubkey_x_squared, L.off_b_slope, L.off_b_x_diff_inv})
+        if (off >= block_rows) return fail(SS_ERR_INVALID, "a cell leaves its block");
+    for (uint32_t off : L.off_pair)
+        if ((off & 1) || off + 1ull >= block_rows) return fail(SS_ERR_INVALID, "a memory-pool pair starts at an even row inside the block");
+    ColPtrs cp{};
+    for (uint32_t c = 0; c < ncols; ++c) cp.dst[c] = d_cols[c];
+    if (!n_given) return SS_OK;
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_ecdsa(ctx->stream, cp, L, (const Fp *)d_points, d_instances, n_given, n_blocks, block_rows, addr_begin, d_pool_addr, d_status));
     return SS_OK;
 }
 namespace {

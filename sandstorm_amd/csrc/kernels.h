@@ -168,7 +168,8 @@ enum { TRACE_ERR_MISSING_CELL = 1, TRACE_ERR_NOT_INSTRUCTION = 2, TRACE_ERR_BAD_
        TRACE_ERR_ADDRESS_RANGE = 32, TRACE_ERR_PUBLIC_ZERO = 64, TRACE_ERR_PUBLIC_CELLS = 128, TRACE_ERR_NO_ONES = 256, TRACE_ERR_NOT_SINGLE_VALUED = 512,
        TRACE_ERR_NOT_CONTINUOUS = 1024, TRACE_ERR_TOO_MANY_GAPS = 2048, TRACE_ERR_FILL = 4096, TRACE_ERR_PEDERSEN_INFINITY = 8192,
        TRACE_ERR_PEDERSEN_INSTANCE = 16384, TRACE_ERR_BITWISE_INSTANCE = 32768, TRACE_ERR_POSEIDON_INSTANCE = 65536,
-       TRACE_ERR_EC_OP_INSTANCE = 131072, TRACE_ERR_EC_OP_DIVISOR = 262144, TRACE_ERR_EC_OP_MEETS = 524288 };
+       TRACE_ERR_EC_OP_INSTANCE = 131072, TRACE_ERR_EC_OP_DIVISOR = 262144, TRACE_ERR_EC_OP_MEETS = 524288,
+       TRACE_ERR_ECDSA_INSTANCE = 1 << 20, TRACE_ERR_ECDSA_INVALID = 1 << 21, TRACE_ERR_ECDSA_DIVISOR = 1 << 22, TRACE_ERR_ECDSA_MEETS = 1 << 23 };
 hipError_t launch_trace_memory_image(hipStream_t st, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells);
 hipError_t launch_trace_cpu(hipStream_t st, const TraceLayout &L, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells,
                             const Fp &pad_value, uint64_t rc_fill, Fp *flags, Fp *npc, Fp *rc, Fp *aux, uint32_t *d_pool_addr, uint32_t *d_status);
@@ -221,6 +222,20 @@ struct TraceEcOpLayout {
 };
 hipError_t launch_trace_ec_op(hipStream_t st, const ColPtrs &cols, const TraceEcOpLayout &L, const uint64_t *d_instances, uint64_t n_given, uint64_t n_blocks,
                               uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
+// an ECDSA instance's cells from the public key (x, y), the message, r and w (= ss_trace_ecdsa_layout), all in column col: step j of half h
+// (0: the key's doubling chain and r Q, 1: B's and w B) at row off_* + row_stride * (256 h + j), step j of the generator's chain at row
+// off_gen_* + gen_stride * j, the eight cells an instance has one of, the two memory-pool pairs (the key's x, the message)
+struct TraceEcdsaLayout {
+    uint32_t col, row_stride, gen_stride;
+    uint32_t off_dbl_x, off_dbl_y, off_dbl_slope, off_sum_x, off_sum_y, off_slope, off_x_diff_inv, off_suffix;
+    uint32_t off_gen_x, off_gen_y, off_gen_slope, off_gen_x_diff_inv, off_gen_suffix;
+    uint32_t off_r_point_slope, off_r_point_x_diff_inv, off_r_inv, off_w_inv, off_message_inv, off_pubkey_x_squared, off_b_slope, off_b_x_diff_inv;
+    uint32_t col_pool, off_pair[2];
+};
+// d_points: TRACE_ECDSA_POINTS affine points, Montgomery (x, y): 2^i G for i <= 250, then the shift point P0
+static constexpr uint32_t TRACE_ECDSA_POINTS = 252, TRACE_ECDSA_SHIFT = 251;
+hipError_t launch_trace_ecdsa(hipStream_t st, const ColPtrs &cols, const TraceEcdsaLayout &L, const Fp *d_points, const uint64_t *d_instances, uint64_t n_given,
+                              uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
 hipError_t launch_trace_ordered_memory(hipStream_t st, const TraceMemoryArgs &m, uint32_t *scratch);
 
 // ---- goldilocks.hip (the 64-bit field variant)

@@ -21,6 +21,8 @@
 //                         rounds and stores every S-box input with its square (the S-box's own intermediate)
 //   trace_ec_op_kernel    the GIVEN EC-op instances from P, Q, m (168 bytes each): one wave per instance - the doubling chain and the
 //                         multiply-add chain in Jacobian coordinates on one lane, then four steps a lane with one inversion each
+//   trace_ecdsa_kernel    the GIVEN ECDSA instances from the key, the message, r and w (168 bytes each): one wave per instance - three
+//                         multiply-add chains and two doubling chains of the EC-op kernel's, run for the key's other root when the first fails
 //   trace_rc_*            the range-check builtin's parts and the pool's ordered values / padding (utils.rs:357-380):
 //                         runs located by binary search in a prefix array of the 65536-bin histogram
 //   trace_runs_kernel     the diluted pool's ordered column the same way
@@ -482,7 +484,7 @@ __global__ __launch_bounds__(64) void trace_poseidon_kernel(ColPtrs cols, TraceP
 // its own steps were touched) and the generation is refused.  An index beyond the blocks or an input with a bit from 252 up: skipped
 // with TRACE_ERR_EC_OP_INSTANCE, nothing written.
 constexpr u32 EC_STEPS = 256, EC_LANES = 64;
-struct EcShared { Fp a[EC_STEPS], b[EC_STEPS], c[EC_STEPS]; u64 rec[21]; u32 divisor, meets; };
+struct EcShared { Fp a[EC_STEPS], b[EC_STEPS], c[EC_STEPS]; u64 rec[21]; u32 divisor, meets, late; };
 struct EcJac { Fp X, Y, Z; };
 __device__ __forceinline__ EcJac ec_jac_double(const EcJac &p) {     // a = 1: M = 3 X^2 + Z^4, S = 4 X Y^2 (host/trace_common.hpp jac_double)
     const Fp xx = fp_sqr(p.X), yy = fp_sqr(p.Y), zz = fp_sqr(p.Z);
@@ -541,7 +543,9 @@ __device__ __forceinline__ int ec_last_set_below(const u64 *x /* 4 */, u32 limit
 struct EcMadStep { Fp x, y, suffix, slope, x_diff_inv; };
 // partial_j = start + the point_i of the set bits i < j of x, point_i = 2^min(i, max_doublings) point = (qx, qy)[qstride * min(i,
 // max_doublings)]: the cells wg_doubling_steps has written.  emit(j, step) takes each of the 256 steps, on the lane that made it.
-// -> false (for every lane) when a partial sum meets its step's point, before anything is emitted; sh.a / b / c are scratch
+// -> false (for every lane) when a partial sum meets its step's point, before anything is emitted: sh.meets when a step up to the
+// scalar's highest set bit does (the steps the reference's mimic_ec_mad_air walks), sh.late when a later one does; sh.a / b / c are
+// scratch
 template <class Emit>
 __device__ __forceinline__ bool wg_ec_mad_steps(EcShared &sh, const u64 *x /* 4 */, const Fp *qx, const Fp *qy, u64 qstride, const Fp &start_x, const Fp &start_y,
                                                 u32 max_doublings, const Emit &emit) {
@@ -570,6 +574,7 @@ __device__ __forceinline__ bool wg_ec_mad_steps(EcShared &sh, const u64 *x /* 4 
     }
     __syncthreads();
     if (sh.meets) return false;
+    const int top = ec_last_set_below(x, EC_STEPS);
     for (u32 pass = 0; pass < 2; ++pass) {                           // every step's difference is looked at before any step is emitted
 #pragma unroll 1
         for (u32 j = t; j < EC_STEPS; j += EC_LANES) {
@@ -578,7 +583,7 @@ __device__ __forceinline__ bool wg_ec_mad_steps(EcShared &sh, const u64 *x /* 4 
             const u32 pi = j < max_doublings ? j : max_doublings;
             const Fp zz = fp_sqr(Z);
             const Fp h = fp_sub(fp_mul(load_fp(&qx[qstride * pi]), zz), X);            // = (point.x - partial.x) Z^2
-            if (pass == 0) { if (fp_is_zero(h)) sh.meets = 1; continue; }
+            if (pass == 0) { if (fp_is_zero(h)) { if ((int)j <= top) sh.meets = 1; else sh.late = 1; } continue; }
             const Fp Y = before < 0 ? start_y : sh.b[before];
             const Fp inv = fp_inv_safegcd(fp_mul(h, Z));
             const Fp zi = fp_mul(h, inv), zi2 = fp_sqr(zi);
@@ -599,7 +604,7 @@ __device__ __forceinline__ bool wg_ec_mad_steps(EcShared &sh, const u64 *x /* 4 
             emit(j, st);
         }
         __syncthreads();
-        if (sh.meets) return false;
+        if (sh.meets | sh.late) return false;
     }
     return true;
 }
@@ -608,7 +613,7 @@ __global__ __launch_bounds__(EC_LANES) void trace_ec_op_kernel(ColPtrs cols, Tra
     __shared__ EcShared sh;
     const u32 t = threadIdx.x;
     if (t < 21) sh.rec[t] = inst[21 * (u64)blockIdx.x + t];
-    if (t == 0) sh.divisor = sh.meets = 0;
+    if (t == 0) sh.divisor = sh.meets = sh.late = 0;
     __syncthreads();
     const u64 *rec = sh.rec;
     const u64 index = rec[0];
@@ -650,6 +655,131 @@ __global__ __launch_bounds__(EC_LANES) void trace_ec_op_kernel(ColPtrs cols, Tra
         const u32 k = t - 1;
         const u32 off = k == 0 ? L.off_pair[0] : k == 1 ? L.off_pair[1] : k == 2 ? L.off_pair[2] : k == 3 ? L.off_pair[3] : L.off_pair[4];      // (selects: no lane-indexed kernel argument)
         ped_pool_pair(pool, pool_addr, base + off, addr0 + k, fp_to_mont(fp_of_words(rec + 1 + 4 * k)));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ ECDSA builtin
+// A given signature from the public key (x and either root y of x^3 + x + beta), the message z, r and w (builtins/src/ecdsa/mod.rs:85-147
+// InstanceTrace::new; starknet trace.rs:428-523; host/trace_starknet.cpp ecdsa_trace and the section's `place` lambda): one wave per
+// instance, three of wg_ec_mad_steps and two of wg_doubling_steps.  z G from -P0 over the constant points 2^i G (its cells do not depend
+// on the root); then, for the canonically larger of y, p - y first (verify, ecdsa/mod.rs:275-304): Q's doubling chain and r Q from P0,
+// B = z G + r Q, B's doubling chain and w B from P0, and the check x(w B - P0) = r.  A candidate that fails the check, or whose partial sum
+// meets its step's point at a step mimic_ec_mad_air walks, is rejected and the other root runs the same way over the same cells (a full
+// second pass: every cell the first wrote is written again); both rejected: TRACE_ERR_ECDSA_INVALID, as a scalar that is zero or has bit
+// 251 set.  A doubling whose y is zero, or a zero z G.x - r Q.x or w B.x - P0.x: TRACE_ERR_ECDSA_DIVISOR; a meeting at a step above the
+// scalar's highest set bit (mimic_ec_mad_air does not see it, gen_ec_mad_steps divides by it): TRACE_ERR_ECDSA_MEETS - both end the
+// instance at the candidate that finds them (with a key on the curve neither is reachable: the start points are fixed and the group's
+// order is prime).  The eight cells an instance has one of are written last: four of them are step-255 cells of the chains.
+struct EcdsaShared { Fp zg[2], end[2], b_slope, b_x_diff_inv, r_slope, r_x_diff_inv; };
+__device__ __forceinline__ bool ecdsa_scalar_ok(const u64 *s /* 4 */) { return (s[0] | s[1] | s[2] | s[3]) && !(s[3] >> 59); }       // 1 <= bit length < 252
+__global__ __launch_bounds__(EC_LANES) void trace_ecdsa_kernel(ColPtrs cols, TraceEcdsaLayout L, const Fp *__restrict__ points, const u64 *__restrict__ inst,
+                                                               u64 n_blocks, u64 block_rows, u64 addr_begin, u32 *__restrict__ pool_addr, u32 *status) {
+    __shared__ EcShared sh;
+    __shared__ EcdsaShared es;
+    const u32 t = threadIdx.x;
+    if (t < 21) sh.rec[t] = inst[21 * (u64)blockIdx.x + t];
+    if (t == 0) sh.divisor = sh.meets = sh.late = 0;
+    __syncthreads();
+    const u64 *rec = sh.rec;
+    const u64 index = rec[0];
+    if (index >= n_blocks || ((rec[4] | rec[8] | rec[12] | rec[16] | rec[20]) >> 60)) {          // (the whole workgroup leaves, here and below)
+        if (t == 0) status_error(status, TRACE_ERR_ECDSA_INSTANCE, blockIdx.x);
+        return;
+    }
+    const u64 *key_y = rec + 5, *message = rec + 9, *r = rec + 13, *w = rec + 17;
+    if (!ecdsa_scalar_ok(message) || !ecdsa_scalar_ok(r) || !ecdsa_scalar_ok(w)) {
+        if (t == 0) status_error(status, TRACE_ERR_ECDSA_INVALID, index);
+        return;
+    }
+    const u64 base = index * block_rows, stride = L.row_stride;
+    Fp *const col = (Fp *)cols.dst[L.col] + base;
+    const Fp *const shift = points + 2 * TRACE_ECDSA_SHIFT;
+    // z G: the sum before step 255 is the whole sum (bit 251 and up are clear)
+    if (!wg_ec_mad_steps(sh, message, points, points + 1, 2, load_fp(shift), fp_neg(load_fp(shift + 1)), TRACE_ECDSA_SHIFT - 1, [&](u32 j, const EcMadStep &st) {
+            const u64 row = (u64)L.gen_stride * j;
+            store_fp(&col[L.off_gen_x + row], st.x); store_fp(&col[L.off_gen_y + row], st.y); store_fp(&col[L.off_gen_slope + row], st.slope);
+            store_fp(&col[L.off_gen_x_diff_inv + row], st.x_diff_inv); store_fp(&col[L.off_gen_suffix + row], st.suffix);
+            if (j == EC_STEPS - 1) { es.zg[0] = st.x; es.zg[1] = st.y; }
+        })) {
+        if (t == 0) status_error(status, sh.meets ? TRACE_ERR_ECDSA_INVALID : TRACE_ERR_ECDSA_MEETS, index);
+        return;
+    }
+    // y >= (p + 1) / 2 = 2^250 + 17 * 2^191 + 1: y is the larger of y, p - y
+    const u64 half_p[4] = {1, 0, 0x8000000000000000ull, 0x0400000000000008ull};
+    bool y_first = true;
+    for (u32 k = 4; k-- > 0;) if (key_y[k] != half_p[k]) { y_first = key_y[k] > half_p[k]; break; }
+    bool accepted = false;
+#pragma unroll 1
+    for (u32 cand = 0; cand < 2 && !accepted; ++cand) {
+        bool rejected = false;
+#pragma unroll 1
+        for (u32 half = 0; half < 2 && !rejected; ++half) {           // 0: Q's doublings and r Q; 1: B's and w B
+            Fp px, py;
+            if (half == 0) {
+                px = fp_to_mont(fp_of_words(rec + 1)); py = fp_to_mont(fp_of_words(key_y));
+                if (y_first != (cand == 0)) py = fp_neg(py);
+            } else {                                                 // B = z G + r Q along the chord (every lane: the values are the wave's)
+                const Fp dx = fp_sub(es.zg[0], es.end[0]);
+                if (fp_is_zero(dx)) {
+                    if (t == 0) status_error(status, TRACE_ERR_ECDSA_DIVISOR, index);
+                    return;
+                }
+                const Fp inv = fp_inv_safegcd(dx), slope = fp_mul(fp_sub(es.zg[1], es.end[1]), inv);
+                px = fp_sub(fp_sub(fp_sqr(slope), es.zg[0]), es.end[0]);
+                py = fp_sub(fp_mul(slope, fp_sub(es.zg[0], px)), es.zg[1]);
+                if (t == 0) { es.b_slope = slope; es.b_x_diff_inv = inv; }
+            }
+            Fp *const c = col + stride * EC_STEPS * half;
+            if (!wg_doubling_steps(sh, px, py, c + L.off_dbl_x, c + L.off_dbl_y, c + L.off_dbl_slope, stride)) {
+                if (t == 0) status_error(status, TRACE_ERR_ECDSA_DIVISOR, index);
+                return;
+            }
+            if (!wg_ec_mad_steps(sh, half ? w : r, c + L.off_dbl_x, c + L.off_dbl_y, stride, load_fp(shift), load_fp(shift + 1), EC_STEPS - 1,
+                                 [&](u32 j, const EcMadStep &st) {
+                    const u64 row = stride * j;
+                    store_fp(&c[L.off_sum_x + row], st.x); store_fp(&c[L.off_sum_y + row], st.y); store_fp(&c[L.off_slope + row], st.slope);
+                    store_fp(&c[L.off_x_diff_inv + row], st.x_diff_inv); store_fp(&c[L.off_suffix + row], st.suffix);
+                    if (j == EC_STEPS - 1) { es.end[0] = st.x; es.end[1] = st.y; }
+                })) {
+                if (!sh.meets) {
+                    if (t == 0) status_error(status, TRACE_ERR_ECDSA_MEETS, index);
+                    return;
+                }
+                __syncthreads();                                     // (every lane has read the flags)
+                if (t == 0) sh.meets = sh.late = 0;
+                __syncthreads();
+                rejected = true;
+            }
+        }
+        if (rejected) continue;
+        // R = w B - P0 along the chord; its x is r
+        const Fp dx = fp_sub(es.end[0], load_fp(shift));
+        if (fp_is_zero(dx)) {
+            if (t == 0) status_error(status, TRACE_ERR_ECDSA_DIVISOR, index);
+            return;
+        }
+        const Fp inv = fp_inv_safegcd(dx), slope = fp_mul(fp_add(es.end[1], load_fp(shift + 1)), inv);
+        accepted = fp_eq(fp_sub(fp_sub(fp_sqr(slope), es.end[0]), load_fp(shift)), fp_to_mont(fp_of_words(r)));
+        if (accepted && t == 0) { es.r_slope = slope; es.r_x_diff_inv = inv; }
+        __syncthreads();                                             // (es.end is read; the other root's chains write it again)
+    }
+    if (!accepted) {
+        if (t == 0) status_error(status, TRACE_ERR_ECDSA_INVALID, index);
+        return;
+    }
+    // the cells an instance has one of, after the steps': four of them lie on step 255 of a chain
+    if (t < 8) {
+        const u32 off = t == 0 ? L.off_w_inv : t == 1 ? L.off_r_inv : t == 2 ? L.off_message_inv : t == 3 ? L.off_r_point_slope : t == 4 ? L.off_r_point_x_diff_inv
+                      : t == 5 ? L.off_pubkey_x_squared : t == 6 ? L.off_b_slope : L.off_b_x_diff_inv;       // (selects: no lane-indexed kernel argument)
+        Fp v;
+        if (t < 3) v = fp_inv_safegcd(fp_to_mont(fp_of_words(t == 0 ? w : t == 1 ? r : message)));
+        else if (t == 5) v = fp_sqr(fp_to_mont(fp_of_words(rec + 1)));
+        else v = t == 3 ? es.r_slope : t == 4 ? es.r_x_diff_inv : t == 6 ? es.b_slope : es.b_x_diff_inv;
+        store_fp(&col[off], v);
+    } else if (t < 10) {
+        const u32 k = t - 8;
+        ped_pool_pair((Fp *)cols.dst[L.col_pool], pool_addr, base + (k ? L.off_pair[1] : L.off_pair[0]), addr_begin + 2 * index + k,
+                      fp_to_mont(fp_of_words(k ? message : rec + 1)));
     }
 }
 
@@ -977,6 +1107,12 @@ hipError_t launch_trace_ec_op(hipStream_t st, const ColPtrs &cols, const TraceEc
                               u64 addr_begin, u32 *d_pool_addr, u32 *d_status) {
     if (!n_given) return hipSuccess;
     hipLaunchKernelGGL(trace_ec_op_kernel, dim3((u32)n_given), dim3(EC_LANES), 0, st, cols, L, d_instances, n_blocks, block_rows, addr_begin, d_pool_addr, d_status);
+    return hipGetLastError();
+}
+hipError_t launch_trace_ecdsa(hipStream_t st, const ColPtrs &cols, const TraceEcdsaLayout &L, const Fp *d_points, const u64 *d_instances, u64 n_given, u64 n_blocks,
+                              u64 block_rows, u64 addr_begin, u32 *d_pool_addr, u32 *d_status) {
+    if (!n_given) return hipSuccess;
+    hipLaunchKernelGGL(trace_ecdsa_kernel, dim3((u32)n_given), dim3(EC_LANES), 0, st, cols, L, d_points, d_instances, n_blocks, block_rows, addr_begin, d_pool_addr, d_status);
     return hipGetLastError();
 }
 hipError_t launch_trace_rc_builtin(hipStream_t st, const TraceRcPlan &p, const u64 *d_given, const uint16_t *d_padding, Fp *rc, Fp *npc, u32 *d_pool_addr) {

@@ -170,3 +170,34 @@ def seeded_ec_op_instances(slots, seed=SEED0):
         point = sk._ec_add(q, sk.GENERATOR)
         rows.append((i, p[0], p[1], q[0], q[1], word(raw[i])))
     return rows
+
+
+def ecdsa_slots(log_steps):
+    """ECDSA builtin instances a 2^log_steps-step starknet trace has room for (the recursive layout has no ECDSA builtin)"""
+    from sandstorm_amd.layouts import starknet as sk
+    return (1 << log_steps) // sk.ECDSA_BUILTIN_RATIO
+
+
+def seeded_ecdsa_instances(slots, seed=SEED0):
+    """`slots` distinct ECDSA instances (index, pubkey_x, message, r, w), one per slot, as air-private-input.json's `ecdsa` rows: honest
+    signatures - private key and message from SplitMix64 (key < 2^240, message < 2^250, both nonzero), the nonces k, k + 1, ... from a
+    seeded k, r = x(k G), w = k / (message + r * key) mod the group's order as the builtin takes it, the next nonce until 0 < r, w < 2^251
+    (the Python mirror's arithmetic, layouts/starknet.py; one affine addition of G per nonce).  The keys, the messages and the nonces
+    differ from slot to slot, and the public key's y is the larger root for about half of the slots"""
+    from sandstorm_amd.layouts import starknet as sk
+    raw = splitmix64_stream(seed ^ 0x45434453, 4 * (2 * slots + 1)).reshape(2 * slots + 1, 4).copy()
+    word = lambda r: sum(int(r[j]) << (64 * j) for j in range(4))
+    k = word(raw[2 * slots]) % (1 << 200) | 1 << 200
+    point = sk._ec_mul(k, sk.GENERATOR)
+    rows = []
+    for i in range(slots):
+        key, message = word(raw[2 * i]) % (1 << 240) | 1, word(raw[2 * i + 1]) % (1 << 250) | 1
+        while True:
+            k, point = k + 1, sk._ec_add(point, sk.GENERATOR)
+            r = point[0]
+            s = (message + r * key) % sk.CURVE_ORDER
+            w = k * pow(s, -1, sk.CURVE_ORDER) % sk.CURVE_ORDER if s else 0
+            if 0 < r < 1 << 251 and 0 < w < 1 << 251:
+                break
+        rows.append((i, sk._ec_mul(key, sk.GENERATOR)[0], message, r, w))
+    return rows

@@ -9,7 +9,8 @@
 //     ss_trace_pedersen makes their cells on the device - only the dummy instance is a template (DeviceTrace::pedersen); the
 //     bitwise builtin's (x, y: 72 bytes) and the Poseidon builtin's (three inputs: 104 bytes) go the same way through ss_trace_bitwise
 //     and ss_trace_poseidon (DeviceTrace::bitwise, DeviceTrace::poseidon), the EC-op builtin's (P, Q, m: 168 bytes) through
-//     ss_trace_ec_op (DeviceTrace::ec_op), and the diluted pool's histogram of the bitwise instances is
+//     ss_trace_ec_op (DeviceTrace::ec_op), the ECDSA builtin's - behind a switch that is off by default - (key, message, r, w: 168 bytes)
+//     through ss_trace_ecdsa (DeviceTrace::ecdsa), and the diluted pool's histogram of the bitwise instances is
 //     counted from their inputs with integer operations (bitwise_count_inputs);
 //   * DeviceTrace uploads the raw files, plans and templates and launches the kernels in the order the host sections run
 //     (a later section overwrites an earlier one's cells, as on the host); the input's errors come back as status bits and are
@@ -199,11 +200,11 @@ struct RcPoolPlan {
 
 // What the last device generation on this thread moved and where its Pedersen instances were traced (ssh_trace_last_stats): the
 // observable behind "no templates for given Pedersen instances" - the cells are the same whichever way they are made
-// (and its bitwise, Poseidon and EC-op instances: ssh_trace_last_stats_n)
+// (and its bitwise, Poseidon, EC-op and ECDSA instances: ssh_trace_last_stats_n)
 struct DeviceTraceStats {
     uint64_t bytes_uploaded = 0, pedersen_on_host = 0, pedersen_on_device = 0, templates_uploaded = 0;
     uint64_t bitwise_on_host = 0, bitwise_on_device = 0, poseidon_on_host = 0, poseidon_on_device = 0;
-    uint64_t ec_op_on_host = 0, ec_op_on_device = 0;
+    uint64_t ec_op_on_host = 0, ec_op_on_device = 0, ecdsa_on_host = 0, ecdsa_on_device = 0;
 };
 inline DeviceTraceStats &device_trace_stats() { static thread_local DeviceTraceStats s; return s; }
 
@@ -403,6 +404,20 @@ class DeviceTrace {
         device_trace_stats().ec_op_on_device += dev.count;
         lap("ec op instances");
     }
+    // the GIVEN ECDSA instances from the key (x and a root y the caller has taken), the message, r and w (csrc/trace.hip
+    // trace_ecdsa_kernel): 168 bytes each go up, the three multiply-add chains and the two doubling chains are made where the cells are,
+    // for the key's other root too when the first does not verify.  points: 2^i G for i <= 250, then the shift point P0 (252 x 2 Montgomery
+    // felts, uploaded once per generation - the device derives no constants).  Called after builtin() has laid the dummy signature's
+    // template over all blocks
+    void ecdsa(DeviceInstances &dev, const ss_trace_ecdsa_layout &layout, const Felt *points, uint64_t block_rows, uint64_t addr_begin, uint64_t host_traced) {
+        device_trace_stats().ecdsa_on_host += host_traced;
+        if (!dev.count) return;
+        const uint64_t *d_points = (const uint64_t *)upload(points, 252 * 2 * sizeof(Felt));
+        const uint64_t *d_recs = upload_vec(std::move(dev.recs));
+        check(ss_trace_ecdsa(ctx_, cols_.data(), ncols_, n_, &layout, d_points, d_recs, dev.count, n_ / block_rows, block_rows, addr_begin, d_pool_addr_, d_status_));
+        device_trace_stats().ecdsa_on_device += dev.count;
+        lap("ecdsa instances");
+    }
     // the range-check pool: plan + histogram -> the pool's cells of every cycle; then (later, in the host sections' order) the builtin
     void rc_pool(ss_trace_rc_plan &plan, const RcPoolPlan &pool, const std::vector<uint32_t> &count, int rc_col) {
         plan.rc_lo = pool.lo; plan.rc_hi = pool.hi; plan.n_padding = pool.padding.size(); plan.pad0 = pool.pad0;
@@ -454,6 +469,10 @@ class DeviceTrace {
         if (err & SS_TRACE_ERR_PEDERSEN_INSTANCE) fail("a Pedersen instance the device was given is beyond the trace's slots or not a pair of field elements");
         if (err & SS_TRACE_ERR_BITWISE_INSTANCE) fail("a bitwise instance the device was given is beyond the trace's slots or not a pair of field elements");
         if (err & SS_TRACE_ERR_POSEIDON_INSTANCE) fail("a Poseidon instance the device was given is beyond the trace's slots or not three field elements");
+        if (err & SS_TRACE_ERR_ECDSA_INSTANCE) fail("an ECDSA instance the device was given is beyond the trace's slots or not five field elements");
+        if (err & SS_TRACE_ERR_ECDSA_INVALID) fail("signature is invalid");                       // (the host generator reaches the ECDSA section before the EC-op one)
+        if (err & SS_TRACE_ERR_ECDSA_DIVISOR) fail("a curve step divides by zero");
+        if (err & SS_TRACE_ERR_ECDSA_MEETS) fail("a partial sum meets the fixed point");
         if (err & SS_TRACE_ERR_EC_OP_INSTANCE) fail("an EC-op instance the device was given is beyond the trace's slots or not five field elements");
         if (err & SS_TRACE_ERR_EC_OP_DIVISOR) fail("a curve step divides by zero");               // (the host generator reaches it before the next)
         if (err & SS_TRACE_ERR_EC_OP_MEETS) fail("a partial sum meets the fixed point");

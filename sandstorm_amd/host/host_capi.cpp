@@ -623,16 +623,21 @@ int ssh_trace_last_stats(uint64_t out[4]) {
 }
 // the same with the buffer's length (ssh_trace_last_stats keeps its four words: its callers pass four): the first min(n_words, 10) of
 // the four words above, then the given bitwise instances traced through a template on the host / on the device from their inputs
-// (ss_trace_bitwise), then the same two for the Poseidon builtin (ss_trace_poseidon) and for the EC-op builtin (ss_trace_ec_op); words
-// beyond the tenth are zeroed
+// (ss_trace_bitwise), then the same two for the Poseidon builtin (ss_trace_poseidon), for the EC-op builtin (ss_trace_ec_op) and for the
+// ECDSA builtin (ss_trace_ecdsa; on the device only with ssh_trace_ecdsa_on_device); words beyond the twelfth are zeroed
 int ssh_trace_last_stats_n(uint64_t *out, uint64_t n_words) {
     if (!out) { g_err = "ssh_trace_last_stats_n: NULL argument"; return 1; }
     const tracedetail::DeviceTraceStats &s = tracedetail::device_trace_stats();
-    const uint64_t all[10] = {s.bytes_uploaded, s.pedersen_on_host, s.pedersen_on_device, s.templates_uploaded, s.bitwise_on_host, s.bitwise_on_device,
-                              s.poseidon_on_host, s.poseidon_on_device, s.ec_op_on_host, s.ec_op_on_device};
-    for (uint64_t k = 0; k < n_words; ++k) out[k] = k < 10 ? all[k] : 0;
+    const uint64_t all[12] = {s.bytes_uploaded, s.pedersen_on_host, s.pedersen_on_device, s.templates_uploaded, s.bitwise_on_host, s.bitwise_on_device,
+                              s.poseidon_on_host, s.poseidon_on_device, s.ec_op_on_host, s.ec_op_on_device, s.ecdsa_on_host, s.ecdsa_on_device};
+    for (uint64_t k = 0; k < n_words; ++k) out[k] = k < 12 ? all[k] : 0;
     return 0;
 }
+// the switch of the ECDSA builtin's device path, process-wide: with a nonzero `on` the device generations that follow trace the given
+// ECDSA instances from their inputs (the host takes the key's square root, ss_trace_ecdsa runs the curve steps) instead of uploading a
+// host-made template per distinct signature.  Off by default: the generation is then what it was before the switch existed.  -> the
+// previous value
+int ssh_trace_ecdsa_on_device(int on) { return set_trace_ecdsa_on_device(on); }
 
 // files -> proof with the base trace made ON the device: trace.bin / memory.bin go up as they are (25 MB where the host-made columns
 // are 3.6 - 4.8 GB of PCIe traffic), csrc/trace.hip makes the columns in d_cols, and the prover goes on as ssh_prove_wire does - what

@@ -2,6 +2,7 @@
 #include "trace_starknet.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -326,6 +327,41 @@ const EcdsaDummy &ecdsa_dummy() {
     return d;
 }
 
+std::atomic<int> g_ecdsa_on_device{0};                    // set_trace_ecdsa_on_device
+// what ss_trace_ecdsa takes as d_points: 2^i G for i <= 250, then the shift point; made once per process
+const std::vector<Felt> &ecdsa_device_points() {
+    static const std::vector<Felt> table = [] {
+        const Curve &cv = curve();
+        std::vector<Jac> dbl(251);
+        dbl[0] = jac_of(cv.generator);
+        for (int i = 1; i < 251; ++i) dbl[i] = jac_double(dbl[i - 1]);
+        std::vector<Felt> v;
+        for (const Pt &p : batch_normalize(dbl)) { v.push_back(p.x); v.push_back(p.y); }
+        v.push_back(cv.shift.x); v.push_back(cv.shift.y);
+        return v;
+    }();
+    return table;
+}
+// the device's records of ECDSA instances (index, key x, message, r, w: 17 words) with a root y of x^3 + x + beta behind the key's x
+// (21 words: ss_trace_ecdsa orders y and p - y itself), the roots taken on all threads; a key that has none is refused here, before
+// anything is uploaded, with ecdsa_trace's message
+void ecdsa_add_roots(DeviceInstances &dev) {
+    const Curve &cv = curve();
+    std::vector<uint64_t> recs(21 * dev.count);
+    parallel_items(dev.count, [&](uint64_t i) {
+        const uint64_t *in = &dev.recs[17 * i];
+        const Felt px = felt_from_canonical(U256{in[1], in[2], in[3], in[4]});
+        Felt y;
+        if (!felt_sqrt(felt_add(felt_add(felt_mul(felt_mul(px, px), px), px), cv.beta), y)) fail("the public key is not on the curve");
+        const U256 yc = canonical_of(y);
+        uint64_t *out = &recs[21 * i];
+        std::copy(in, in + 5, out);
+        std::copy(yc.begin(), yc.end(), out + 5);
+        std::copy(in + 5, in + 17, out + 9);
+    });
+    dev.recs = std::move(recs);
+}
+
 const ss_trace_layout &cpu_layout() {                     // the CPU's cells in a cycle's 16 rows (starknet air.rs:2538-3250: Npc, RangeCheck, Auxiliary)
     static const ss_trace_layout l = [] {
         ss_trace_layout v;
@@ -501,12 +537,15 @@ struct HostBackend {
     void bitwise_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
     void poseidon_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
     void ec_op_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
+    static constexpr bool ecdsa_on_device = false;
+    void ecdsa_given(DeviceInstances &, uint64_t, uint64_t, uint64_t) {}
 };
 
 // ---- the device backend: the same sections as uploads of plans / templates and kernel launches (device_trace.hpp, csrc/trace.hip)
 struct DeviceBackend {
     const Inputs &in;
     DeviceTrace &dt;
+    void lap(const char *what) { dt.lap(what); }
     void cpu_section(const RcPoolPlan &pool, const std::vector<uint32_t> &rc_count, uint64_t rc_fill) {
         dt.cpu_cells(cpu_layout(), COL_FLAGS, COL_NPC, COL_RANGE_CHECK, COL_AUXILIARY, in.pad_value, rc_fill);
         ss_trace_rc_plan plan{};
@@ -566,6 +605,21 @@ struct DeviceBackend {
         l.col_pool = COL_NPC;
         for (int k = 0; k < 7; ++k) l.off_pair[k] = (uint32_t)NPC_EC_OP_ADDRS[k];
         dt.ec_op(dev, l, step, begin, host_traced);
+    }
+    // and, with set_trace_ecdsa_on_device, the given ECDSA instances: ss_trace_ecdsa makes the cells the section's `place` lambda names
+    static constexpr bool ecdsa_on_device = true;
+    void ecdsa_given(DeviceInstances &dev, uint64_t step, uint64_t begin, uint64_t host_traced) {
+        ss_trace_ecdsa_layout l{};
+        l.col = COL_AUXILIARY; l.row_stride = 64; l.gen_stride = 128;
+        l.off_dbl_x = EC_PUBKEY_DOUBLING_X; l.off_dbl_y = EC_PUBKEY_DOUBLING_Y; l.off_dbl_slope = EC_PUBKEY_DOUBLING_SLOPE;
+        l.off_sum_x = EC_PUBKEY_PARTIAL_SUM_X; l.off_sum_y = EC_PUBKEY_PARTIAL_SUM_Y; l.off_slope = EC_PUBKEY_PARTIAL_SUM_SLOPE;
+        l.off_x_diff_inv = EC_PUBKEY_PARTIAL_SUM_X_DIFF_INV; l.off_suffix = EC_R_SUFFIX;
+        l.off_gen_x = EC_GENERATOR_PARTIAL_SUM_X; l.off_gen_y = EC_GENERATOR_PARTIAL_SUM_Y; l.off_gen_slope = EC_GENERATOR_PARTIAL_SUM_SLOPE;
+        l.off_gen_x_diff_inv = EC_GENERATOR_PARTIAL_SUM_X_DIFF_INV; l.off_gen_suffix = EC_MESSAGE_SUFFIX;
+        l.off_r_point_slope = EC_R_POINT_SLOPE; l.off_r_point_x_diff_inv = EC_R_POINT_X_DIFF_INV; l.off_r_inv = EC_R_INV; l.off_w_inv = EC_W_INV;
+        l.off_message_inv = EC_MESSAGE_INV; l.off_pubkey_x_squared = EC_PUBKEY_X_SQUARED; l.off_b_slope = EC_B_SLOPE; l.off_b_x_diff_inv = EC_B_X_DIFF_INV;
+        l.col_pool = COL_NPC; l.off_pair[0] = NPC_ECDSA_PUBKEY_ADDR; l.off_pair[1] = NPC_ECDSA_MESSAGE_ADDR;
+        dt.ecdsa(dev, l, ecdsa_device_points().data(), step, begin, host_traced);
     }
 };
 
@@ -642,9 +696,19 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
     {
         const uint64_t step = ECDSA_BUILTIN_RATIO * CYCLE_HEIGHT;
         const auto given = instances_by_index(priv.ecdsa, n / step, "ecdsa");
+        // with the switch on, the device makes the given instances' cells from the key, the message, r and w (ecdsa_given below: the host
+        // takes the key's square root, the curve steps run where the cells are) and takes the dummy signature as its one template
+        DeviceInstances dev = device_instances(Backend::ecdsa_on_device && g_ecdsa_on_device.load() != 0, priv.ecdsa, n / step, 4, [](const EcdsaInstance &e, unsigned k) -> const U256 & {
+            return k == 0 ? e.pubkey_x : k == 1 ? e.message : k == 2 ? e.r : e.w;
+        });
+        if (dev.count) {                                     // (SSH_TRACE_TIMING: the roots' time on a line of its own)
+            be.lap("range-check builtin");
+            ecdsa_add_roots(dev);
+            be.lap("ecdsa roots");
+        }
         Instances<U256x4, EcdsaTrace> inst;
         inst.assign(n / step, [&](uint64_t i) {
-            auto it = given.find((uint32_t)i);
+            auto it = dev.holds(i) ? given.end() : given.find((uint32_t)i);
             return it != given.end() ? U256x4{it->second->pubkey_x, it->second->message, it->second->r, it->second->w} : ecdsa_dummy().key;
         });
         inst.trace_all([](const U256x4 &k) {               // (three scalar multiplications with their doubling chains per signature)
@@ -679,6 +743,7 @@ template <class Backend> void generate(Backend &be, const Inputs &in) {
             s.pair(NPC_ECDSA_PUBKEY_ADDR, 0, t.pubkey.x);
             s.pair(NPC_ECDSA_MESSAGE_ADDR, 1, t.message);
         });
+        be.ecdsa_given(dev, step, pi.segments[5].begin_addr, (uint64_t)std::count_if(inst.keys.begin(), inst.keys.end(), [](const U256x4 &k) { return k != ecdsa_dummy().key; }));
     }
     // ---- bitwise and the diluted check (trace.rs:525-705)
     {
@@ -815,6 +880,8 @@ Inputs check_inputs(const RegisterStates &states, const Mem &mem, const AirPubli
 }
 
 }  // namespace
+
+int set_trace_ecdsa_on_device(int on) { return g_ecdsa_on_device.exchange(on ? 1 : 0); }
 
 void starknet_base_trace_into(Felt *const out[9], const RegisterStates &states, const std::vector<U256> &memory,
                               const std::vector<uint8_t> &present, const AirPublicInput &pi, const StarknetPrivateInput &priv,

@@ -40,6 +40,10 @@ void starknet_base_trace_device(ss_ctx *ctx, uint64_t *const d_cols[9], const ui
                                 uint64_t memory_len, const std::vector<U256> &memory, const std::vector<uint8_t> &present, const AirPublicInput &pi,
                                 const StarknetPrivateInput &priv);
 
+// the process-wide switch behind ssh_trace_ecdsa_on_device: starknet_base_trace_device traces the given ECDSA instances on the device from
+// their inputs (ss_trace_ecdsa) instead of uploading a host-made template per distinct signature.  Off by default.  -> the previous value
+int set_trace_ecdsa_on_device(int on);
+
 // shared with the AIR (air_starknet.cpp): StarkWare's Hades round constants, the curve's generator and beta
 const std::vector<std::array<Felt, 3>> &poseidon_round_keys();
 void starknet_curve(Felt &generator_x, Felt &generator_y, Felt &beta);

@@ -690,7 +690,7 @@ def device_base_trace(ctx, layout, trace_bin: bytes, memory_bin: bytes, pi, priv
 
 
 TRACE_STATS_KEYS = ("bytes_uploaded", "pedersen_on_host", "pedersen_on_device", "templates_uploaded", "bitwise_on_host", "bitwise_on_device", "poseidon_on_host",
-                    "poseidon_on_device", "ec_op_on_host", "ec_op_on_device")
+                    "poseidon_on_device", "ec_op_on_host", "ec_op_on_device", "ecdsa_on_host", "ecdsa_on_device")
 
 
 def trace_last_stats():
@@ -698,12 +698,22 @@ def trace_last_stats():
     -> {"bytes_uploaded", "pedersen_on_host", "pedersen_on_device", "templates_uploaded"}: the generator's uploads in bytes, the given
     Pedersen instances whose curve steps ran on the host / on the device, the builtin templates uploaded (all builtins); and
     {"bitwise_on_host", "bitwise_on_device", "poseidon_on_host", "poseidon_on_device", "ec_op_on_host", "ec_op_on_device"}: the given
-    bitwise / Poseidon / EC-op instances that went through a host-made template / were traced on the device from their inputs"""
+    bitwise / Poseidon / EC-op instances that went through a host-made template / were traced on the device from their inputs; and
+    {"ecdsa_on_host", "ecdsa_on_device"}: the same for the given ECDSA instances - on the device only after trace_ecdsa_on_device(True)"""
     out = (C.c_uint64 * len(TRACE_STATS_KEYS))()
     fn = load().ssh_trace_last_stats_n
     fn.argtypes = [C.POINTER(C.c_uint64), C.c_uint64]
     _check(fn(out, len(TRACE_STATS_KEYS)))
     return {k: int(out[i]) for i, k in enumerate(TRACE_STATS_KEYS)}
+
+
+def trace_ecdsa_on_device(on):
+    """the process-wide switch of the ECDSA builtin's device path (host_capi.cpp ssh_trace_ecdsa_on_device): when on, device_base_trace
+    and prove_files_device trace the given ECDSA instances on the device from their inputs (168 bytes each) instead of uploading a
+    host-made template (172 KB) per distinct signature.  Off by default.  -> the previous value"""
+    fn = load().ssh_trace_ecdsa_on_device
+    fn.argtypes, fn.restype = [C.c_int], C.c_int
+    return bool(fn(1 if on else 0))
 
 
 def prove_files_device(ctx, layout, trace_bin: bytes, memory_bin: bytes, pi, private_input, dev_cols, air: HostAir, tree_kind, n_friendly, coin_kind, seed,

@@ -16,7 +16,7 @@ SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int": "c_int"
            "ss_perm_operand": "SsPermOperand", "ss_gather_job": "SsGatherJob", "uint16_t": "u16", "ss_trace_layout": "SsTraceLayout",
            "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan", "ss_trace_pedersen_layout": "SsTracePedersenLayout",
            "ss_trace_bitwise_layout": "SsTraceBitwiseLayout", "ss_trace_poseidon_layout": "SsTracePoseidonLayout",
-           "ss_trace_ec_op_layout": "SsTraceEcOpLayout"}
+           "ss_trace_ec_op_layout": "SsTraceEcOpLayout", "ss_trace_ecdsa_layout": "SsTraceEcdsaLayout"}
 
 
 def prototypes(text=None):
@@ -98,6 +98,12 @@ def rust_block():
              "#[repr(C)] pub struct SsTraceEcOpLayout {     // ss_trace_ec_op_layout",
              "    pub col: u32, pub row_stride: u32, pub off_dbl_x: u32, pub off_dbl_y: u32, pub off_dbl_slope: u32, pub off_sum_x: u32, pub off_sum_y: u32, pub off_suffix: u32,",
              "    pub off_slope: u32, pub off_x_diff_inv: u32, pub off_flag2: u32, pub off_flag3: u32, pub col_pool: u32, pub off_pair: [u32; 7],", "}",
+             "#[repr(C)] pub struct SsTraceEcdsaLayout {    // ss_trace_ecdsa_layout",
+             "    pub col: u32, pub row_stride: u32, pub gen_stride: u32,",
+             "    pub off_dbl_x: u32, pub off_dbl_y: u32, pub off_dbl_slope: u32, pub off_sum_x: u32, pub off_sum_y: u32, pub off_slope: u32, pub off_x_diff_inv: u32, pub off_suffix: u32,",
+             "    pub off_gen_x: u32, pub off_gen_y: u32, pub off_gen_slope: u32, pub off_gen_x_diff_inv: u32, pub off_gen_suffix: u32,",
+             "    pub off_r_point_slope: u32, pub off_r_point_x_diff_inv: u32, pub off_r_inv: u32, pub off_w_inv: u32, pub off_message_inv: u32, pub off_pubkey_x_squared: u32,",
+             "    pub off_b_slope: u32, pub off_b_x_diff_inv: u32, pub col_pool: u32, pub off_pair: [u32; 2],", "}",
              "#[link(name = \"sandstorm_hip\")]", "extern \"C\" {"]
     for name, ret, params in prototypes():
         args = ", ".join("%s: %s" % (p if p not in ("in", "type", "ref", "mod") else p + "_", rust_type(t)) for t, p in params)
