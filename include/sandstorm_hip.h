@@ -733,6 +733,43 @@ ss_status ss_trace_patch(ss_ctx *ctx, uint64_t *d_col, uint64_t col_rows, const 
 ss_status ss_trace_ordered_memory(ss_ctx *ctx, uint64_t n, uint64_t *d_pool, uint64_t *d_memory, uint32_t *d_pool_addr, const uint32_t *d_public_addr,
                                   const uint64_t *d_public_value, uint32_t n_public, uint64_t public_cells, const uint64_t pad_value[4],
                                   uint32_t unused_off, uint32_t *d_status);
+/* ---- the base trace of the PLAIN layout over the 64-bit field p = 2^64 - 2^32 + 1 (the claim of cli/src/main.rs:103-133; ExecutionTrace::new,
+ *      layouts/src/plain/trace.rs:60-262, which cli/src/main.rs:186-202 runs inside its "Proof generated in" timer).  The pipeline above over
+ *      one-word cells: five columns of n = 16 * num_cycles plain u64 values below p - NOT Montgomery: what every *_gl64* entry point takes -
+ *      with that layout's placement, the only one the field has (layouts/src/plain/air.rs:560-760):
+ *        flags        the 16 flag prefixes
+ *        pool (Npc)   (pc, instruction) at rows 0, 1; (op0) 4, 5; (dst) 8, 9; (op1) 12, 13; the public-memory slots (0, 0) at 2, 3 and 10, 11; the
+ *                     padding pair (1, value at address 1) at 6, 7 and 14, 15 - the latter the gap cell (Npc::GapAddr / GapVal)
+ *        range check  off_dst / off_op1 / off_op0 at 0 / 4 / 8; ap, op0 * op1, fp, res at 3 / 7 / 11 / 15; the ordered values at 4 j + 2 and the
+ *                     unused value at 12 (ss_trace_gl64_rc_pool); the filler rc_fill at 1, 5, 9, 13
+ *        auxiliary    tmp0 at 0, tmp1 at 8, zero elsewhere
+ *      Same stream, same status block and SS_TRACE_ERR_* bits as above, with one difference: the CPU's five error bits (MISSING_CELL ..
+ *      NOT_AN_ADDRESS, bits b = 0 .. 4) each name their smallest cycle in a word of their own, status[SS_TRACE_STATUS_GL_CYCLE + b] = ~cycle, and
+ *      word 1 names addresses only (the ordered memory's errors): a location is never reported for another error's bit.  Every writer takes
+ *      the columns' length col_rows and refuses a size that would write past it. */
+#define SS_TRACE_STATUS_GL_CYCLE 7u
+/* memory.bin (plain/trace.rs:60-75 reads it through binary/src/lib.rs Memory): d_image[address] = the record's word as ONE u64.  All ones
+ * (>= p: no field element) marks a cell no record names and a cell whose word has a nonzero upper 24 bytes or a low word >= p: the run
+ * that reads it is refused as a missing cell.  Records at or beyond `cells` are dropped. */
+ss_status ss_trace_gl64_memory_image(ss_ctx *ctx, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells);
+/* The CPU's cells (plain/trace.rs:100-215): one lane per cycle decodes the word at pc, reads dst / op0 / op1 from d_image, computes res
+ * (dst^-1 for a conditional jump, zero for dst = 0), tmp0, tmp1 and op0 * op1; the workgroup writes the cycle's 16 rows of the four
+ * columns whole, and the pool's 8 addresses per cycle into d_pool_addr (n / 2 u32).  pad_value: the value at address 1.  An op0 used as
+ * an address that has more than 32 bits sets SS_TRACE_ERR_NOT_AN_ADDRESS. */
+ss_status ss_trace_gl64_cpu_cells(ss_ctx *ctx, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells, uint64_t pad_value,
+                                  uint64_t rc_fill, uint64_t col_rows, uint64_t *d_flags, uint64_t *d_pool, uint64_t *d_range_check, uint64_t *d_auxiliary,
+                                  uint32_t *d_pool_addr, uint32_t *d_status);
+/* The range-check pool (plain/trace.rs:216-240; utils.rs:357-380) from the plan ss_trace_rc_pool takes (ordered_step 4, ordered_off 2,
+ * unused_off 12; d_first, d_padding as there): the ordered values at rows 4 j + 2 and padding value pad0 + c at row 12 of EVERY cycle c -
+ * the 252-bit layouts place one on odd cycles -, then rc_hi forever. */
+ss_status ss_trace_gl64_rc_pool(ss_ctx *ctx, const ss_trace_rc_plan *plan, const uint32_t *d_first, const uint16_t *d_padding, uint64_t num_cycles, uint64_t col_rows,
+                                uint64_t *d_range_check);
+/* The gap cells and the ordered memory column (plain/trace.rs:92-98, 241-262; utils.rs:112-152), as ss_trace_ordered_memory: counts per
+ * address from d_pool_addr and the public memory (d_public_value: values below p; the other n / 8 - n_public entries are (1, pad_value)),
+ * the unaccessed addresses between the lowest and the highest as (address, 0) at rows 14, 15 of cycles 0, 1, ..., the sorted (address,
+ * value) pairs into d_memory's even / odd rows; the reference's checks set the same SS_TRACE_ERR_* bits. */
+ss_status ss_trace_gl64_ordered_memory(ss_ctx *ctx, uint64_t n, uint64_t col_rows, uint64_t *d_pool, uint64_t *d_memory, uint32_t *d_pool_addr,
+                                       const uint32_t *d_public_addr, const uint64_t *d_public_value, uint32_t n_public, uint64_t pad_value, uint32_t *d_status);
 /* waits for the stream and reads the status block (SS_TRACE_STATUS_WORDS u32) */
 ss_status ss_trace_status(ss_ctx *ctx, const uint32_t *d_status, uint32_t *status_out);
 

@@ -1669,6 +1669,54 @@ ss_status ss_trace_ordered_memory(ss_ctx *ctx, uint64_t n, uint64_t *d_pool, uin
     HIP_TRY(launch_trace_ordered_memory(ctx->stream, m, (uint32_t *)ctx->scratch));
     return SS_OK;
 }
+// ---- the plain layout over the 64-bit field (trace.hip trace_gl64_* / mem_*_gl64): every writer takes the columns' length
+static_assert(SS_TRACE_STATUS_GL_CYCLE == TRACE_ST_GL_CYCLE && SS_TRACE_STATUS_GL_CYCLE + TRACE_GL_CPU_ERROR_BITS <= SS_TRACE_STATUS_WORDS, "the header's constants are the kernels'");
+ss_status ss_trace_gl64_memory_image(ss_ctx *ctx, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells) {
+    if (!ctx || !d_image || (n_records && !d_records)) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!cells || cells > (1ull << 33)) return fail(SS_ERR_INVALID, "memory image of %llu cells", (unsigned long long)cells);
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_gl64_memory_image(ctx->stream, d_records, n_records, d_image, cells));
+    return SS_OK;
+}
+ss_status ss_trace_gl64_cpu_cells(ss_ctx *ctx, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells, uint64_t pad_value,
+                                  uint64_t rc_fill, uint64_t col_rows, uint64_t *d_flags, uint64_t *d_pool, uint64_t *d_range_check, uint64_t *d_auxiliary,
+                                  uint32_t *d_pool_addr, uint32_t *d_status) {
+    if (!ctx || !d_states || !d_image || !d_flags || !d_pool || !d_range_check || !d_auxiliary || !d_pool_addr || !d_status) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!num_cycles || num_cycles > (1ull << 28)) return fail(SS_ERR_INVALID, "num_cycles out of range");
+    if (16 * num_cycles > col_rows) return fail(SS_ERR_INVALID, "%llu cycles do not fit columns of %llu rows", (unsigned long long)num_cycles, (unsigned long long)col_rows);
+    if (pad_value >= GL_P || rc_fill >= 65536) return fail(SS_ERR_INVALID, "the padding value is below p, the filler has 16 bits");
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_gl64_cpu(ctx->stream, d_states, num_cycles, d_image, cells, pad_value, rc_fill, d_flags, d_pool, d_range_check, d_auxiliary, d_pool_addr,
+                                  d_status));
+    return SS_OK;
+}
+ss_status ss_trace_gl64_rc_pool(ss_ctx *ctx, const ss_trace_rc_plan *plan, const uint32_t *d_first, const uint16_t *d_padding, uint64_t num_cycles, uint64_t col_rows,
+                                uint64_t *d_range_check) {
+    if (!ctx || !d_first || !d_range_check || (plan && plan->n_padding && !d_padding)) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!rc_plan_ok(plan) || plan->ordered_step != 4 || plan->ordered_off != 2 || plan->unused_off != 12)
+        return fail(SS_ERR_INVALID, "bad range-check plan (the plain layout: ordered values at 4 j + 2, the unused value at 12)");
+    if (!num_cycles || num_cycles > (1ull << 28)) return fail(SS_ERR_INVALID, "num_cycles out of range");
+    if (16 * num_cycles > col_rows) return fail(SS_ERR_INVALID, "%llu cycles do not fit a column of %llu rows", (unsigned long long)num_cycles, (unsigned long long)col_rows);
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_gl64_rc_pool(ctx->stream, rc_plan_of(plan), d_first, d_padding, num_cycles, d_range_check));
+    return SS_OK;
+}
+ss_status ss_trace_gl64_ordered_memory(ss_ctx *ctx, uint64_t n, uint64_t col_rows, uint64_t *d_pool, uint64_t *d_memory, uint32_t *d_pool_addr,
+                                       const uint32_t *d_public_addr, const uint64_t *d_public_value, uint32_t n_public, uint64_t pad_value, uint32_t *d_status) {
+    if (!ctx || !d_pool || !d_memory || !d_pool_addr || !d_status || (n_public && (!d_public_addr || !d_public_value))) return fail(SS_ERR_INVALID, "NULL argument");
+    if (n < 16 || (n & (n - 1)) || n > (1ull << 32)) return fail(SS_ERR_INVALID, "n must be a power of two in [16, 2^32]");
+    if (n > col_rows) return fail(SS_ERR_INVALID, "%llu rows do not fit columns of %llu rows", (unsigned long long)n, (unsigned long long)col_rows);
+    if (n_public > n / 8) return fail(SS_ERR_INVALID, "public memory does not fit its cells");
+    if (pad_value >= GL_P) return fail(SS_ERR_INVALID, "the padding value is below p");
+    ss_status st = ctx->ensure_scratch(trace_memory_scratch_words(n / 2) * sizeof(uint32_t));
+    if (st != SS_OK) return st;
+    TraceGl64MemoryArgs m;
+    m.n = n; m.npc = d_pool; m.memory = d_memory; m.d_pool_addr = d_pool_addr; m.d_public_addr = d_public_addr; m.d_public_value = d_public_value;
+    m.n_public = n_public; m.pad_value = pad_value; m.d_status = d_status;
+    ss_ctx::Scope prof(ctx, SS_PROF_TRACE);
+    HIP_TRY(launch_trace_gl64_ordered_memory(ctx->stream, m, (uint32_t *)ctx->scratch));
+    return SS_OK;
+}
 ss_status ss_trace_status(ss_ctx *ctx, const uint32_t *d_status, uint32_t *status_out) {
     if (!ctx || !d_status || !status_out) return fail(SS_ERR_INVALID, "NULL argument");
     HIP_TRY(hipMemcpyAsync(status_out, d_status, SS_TRACE_STATUS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));

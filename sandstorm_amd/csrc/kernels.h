@@ -163,7 +163,10 @@ struct TraceMemoryArgs {
     uint32_t *d_status;
 };
 // the status words of a generation (u32, zeroed by the caller before the first kernel)
-enum { TRACE_ST_ERRORS = 0, TRACE_ST_WHERE = 1, TRACE_ST_ZEROS = 2, TRACE_ST_ONES = 3, TRACE_ST_TOP = 4, TRACE_ST_NLOW = 5, TRACE_ST_GAPS = 6, TRACE_ST_WORDS = 16 };
+enum { TRACE_ST_ERRORS = 0, TRACE_ST_WHERE = 1, TRACE_ST_ZEROS = 2, TRACE_ST_ONES = 3, TRACE_ST_TOP = 4, TRACE_ST_NLOW = 5, TRACE_ST_GAPS = 6,
+       TRACE_ST_GL_CYCLE = 7,        // the 64-bit field's CPU kernel: word 7 + b = ~(the smallest cycle that raised error bit b), b < TRACE_GL_CPU_ERROR_BITS
+       TRACE_ST_WORDS = 16 };
+static constexpr uint32_t TRACE_GL_CPU_ERROR_BITS = 5;             // MISSING_CELL .. NOT_AN_ADDRESS
 enum { TRACE_ERR_MISSING_CELL = 1, TRACE_ERR_NOT_INSTRUCTION = 2, TRACE_ERR_BAD_OP1_SOURCE = 4, TRACE_ERR_BAD_RES_LOGIC = 8, TRACE_ERR_NOT_AN_ADDRESS = 16,
        TRACE_ERR_ADDRESS_RANGE = 32, TRACE_ERR_PUBLIC_ZERO = 64, TRACE_ERR_PUBLIC_CELLS = 128, TRACE_ERR_NO_ONES = 256, TRACE_ERR_NOT_SINGLE_VALUED = 512,
        TRACE_ERR_NOT_CONTINUOUS = 1024, TRACE_ERR_TOO_MANY_GAPS = 2048, TRACE_ERR_FILL = 4096, TRACE_ERR_PEDERSEN_INFINITY = 8192,
@@ -237,6 +240,22 @@ static constexpr uint32_t TRACE_ECDSA_POINTS = 252, TRACE_ECDSA_SHIFT = 251;
 hipError_t launch_trace_ecdsa(hipStream_t st, const ColPtrs &cols, const TraceEcdsaLayout &L, const Fp *d_points, const uint64_t *d_instances, uint64_t n_given,
                               uint64_t n_blocks, uint64_t block_rows, uint64_t addr_begin, uint32_t *d_pool_addr, uint32_t *d_status);
 hipError_t launch_trace_ordered_memory(hipStream_t st, const TraceMemoryArgs &m, uint32_t *scratch);
+// the plain layout over the 64-bit field (ss_trace_gl64_*): columns of canonical u64 values, the placement of layouts/src/plain
+hipError_t launch_trace_gl64_memory_image(hipStream_t st, const uint64_t *d_records, uint64_t n_records, uint64_t *d_image, uint64_t cells);
+hipError_t launch_trace_gl64_cpu(hipStream_t st, const uint64_t *d_states, uint64_t num_cycles, const uint64_t *d_image, uint64_t cells, uint64_t pad_value,
+                                 uint64_t rc_fill, uint64_t *flags, uint64_t *npc, uint64_t *rc, uint64_t *aux, uint32_t *d_pool_addr, uint32_t *d_status);
+hipError_t launch_trace_gl64_rc_pool(hipStream_t st, const TraceRcPlan &p, const uint32_t *d_first, const uint16_t *d_padding, uint64_t num_cycles, uint64_t *rc);
+struct TraceGl64MemoryArgs {
+    uint64_t n;                       // trace rows
+    uint64_t *npc, *memory;           // the memory pool's column, the ordered column
+    uint32_t *d_pool_addr;            // n / 2
+    const uint32_t *d_public_addr;    // the public memory's entries: addresses, values below p
+    const uint64_t *d_public_value;
+    uint32_t n_public;
+    uint64_t pad_value;               // the value at address 1
+    uint32_t *d_status;
+};
+hipError_t launch_trace_gl64_ordered_memory(hipStream_t st, const TraceGl64MemoryArgs &m, uint32_t *scratch);
 
 // ---- goldilocks.hip (the 64-bit field variant)
 uint64_t gl_pow_host(uint64_t a, uint64_t e);

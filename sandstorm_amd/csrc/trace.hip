@@ -31,9 +31,13 @@
 //                         table per workgroup (an idling run reads the same handful of cells a million times), gaps by a
 //                         flag scan, a prefix sum over the counts, rows by binary search in it; the reference's checks
 //                         (continuous, single-valued, public memory = the address-0 cells) as error bits in a status word
+//   trace_gl64_* / mem_*_gl64   the plain layout over the 64-bit field (layouts/src/plain/trace.rs:60-262): the same pipeline over one-word
+//                         cells, canonical (not Montgomery), with that layout's placement; the counting half of the ordered memory -
+//                         u32 addresses, no field - is the kernels above, launched as they are
 // HBM-write bound: ~5 GB written once.  No floating point, no MFMA: integer decode and a handful of modular products per cell.
 #include <hip/hip_runtime.h>
 #include "inv252.h"
+#include "gl64.h"
 #include "kernels.h"
 
 namespace ss {
@@ -1059,6 +1063,183 @@ __global__ void mem_fill_total_kernel(const u32 *__restrict__ start, u64 half, u
     if (start[2] == 0) status_error(status, TRACE_ERR_NO_ONES, 1);     // start[2] = accesses of address 1 (start[0] = start[1] = 0)
 }
 
+// ------------------------------------------------------------------------------------------------ the plain layout over the 64-bit field
+// ExecutionTrace::new of layouts/src/plain/trace.rs:60-262 (restated cell for cell by sandstorm_amd/layouts/plain.py base_trace): five
+// columns of canonical u64 values below p = 2^64 - 2^32 + 1 (gl64.h), not Montgomery - what every *_gl64* entry point takes.  The field has
+// this one layout, so the placement is written out here instead of coming in as tables:
+//   flags        the 16 prefix values
+//   pool (Npc)   pairs 0 / 2 / 4 / 6 = (pc, instruction), (op0), (dst), (op1); pairs 1 and 5 the public-memory slots (0, 0); pairs 3 and 7
+//                the padding pair (1, value at 1) - pair 7 is the gap cell mem_gap_fill_gl64_kernel takes
+//   range check  offsets 0 / 4 / 8 = off_dst / off_op1 / off_op0; 3 / 7 / 11 / 15 = ap / op0 * op1 / fp / res; 2 + 4 j the ordered values
+//                and 12 the unused value (trace_gl64_rc_pool_kernel); the filler elsewhere
+//   auxiliary    tmp0 at 0, tmp1 at 8, zero elsewhere
+// The memory image holds one u64 per cell; all ones (>= p: no field element) marks a cell no record names, or whose word is no field element.
+// A CPU error names its cycle in a status word of ITS OWN BIT (TRACE_ST_GL_CYCLE + bit number): the ordered memory's errors name
+// addresses in TRACE_ST_WHERE, and a cycle of one error is never reported for another.
+__global__ __launch_bounds__(256) void trace_gl64_memory_image_kernel(const u64 *__restrict__ records, u64 n_records, u64 *__restrict__ image, u64 cells) {
+    const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_records) return;
+    const u64 a = records[5 * k];
+    if (a >= cells) return;
+    const u64 w = records[5 * k + 1];
+    if ((records[5 * k + 2] | records[5 * k + 3] | records[5 * k + 4]) || w >= GL_P) return;      // no field element: the cell keeps the mark
+    image[a] = w;
+}
+
+struct GlCpuRec {
+    u64 word, ap, fp;
+    u64 val[4];                              // the instruction word, op0, dst, op1 (REC_*)
+    u64 res, tmp1, mul;
+    u32 addr[4];                             // pc, op0, dst, op1, saturated as in CpuRec
+    u32 jnz, pad;
+};
+__device__ __forceinline__ bool gl_image_cell(const u64 *image, u64 cells, u64 a, u64 &w) {
+    w = 0;
+    if (a >= cells) return false;
+    const u64 v = image[a];
+    if (v >= GL_P) return false;
+    w = v;
+    return true;
+}
+__device__ __forceinline__ void gl_cpu_error(u32 *status, u32 bits, u64 cyc) {
+    atomicOr(&status[TRACE_ST_ERRORS], bits);
+#pragma unroll
+    for (u32 b = 0; b < TRACE_GL_CPU_ERROR_BITS; ++b)
+        if ((bits >> b) & 1) atomicMax(&status[TRACE_ST_GL_CYCLE + b], ~sat32(cyc));
+}
+
+__global__ __launch_bounds__(CPU_CYC) void trace_gl64_cpu_kernel(const u64 *__restrict__ states, u64 num_cycles, const u64 *__restrict__ image, u64 cells, u64 pad_value,
+                                                                 u64 rc_fill, u64 *__restrict__ flags, u64 *__restrict__ npc, u64 *__restrict__ rc, u64 *__restrict__ aux,
+                                                                 u32 *__restrict__ pool_addr, u32 *status) {
+    __shared__ GlCpuRec rec[CPU_CYC];
+    const u32 t = threadIdx.x;
+    const u64 cyc0 = (u64)blockIdx.x * CPU_CYC, cyc = cyc0 + t;
+    if (cyc < num_cycles) {
+        GlCpuRec &r = rec[t];
+        const u64 ap = states[3 * cyc], fp = states[3 * cyc + 1], pc = states[3 * cyc + 2];
+        u32 err = 0;
+        u64 w, op0, dst, op1;
+        if (!gl_image_cell(image, cells, pc, w)) err |= TRACE_ERR_MISSING_CELL;
+        if (w >> 63) err |= TRACE_ERR_NOT_INSTRUCTION;
+        auto flag = [&](int f) { return (u32)((w >> (48 + f)) & 1); };
+        const u64 dst_addr = (w & 0xffff) + (flag(0) ? fp : ap) - 0x8000, op0_addr = ((w >> 16) & 0xffff) + (flag(1) ? fp : ap) - 0x8000;
+        if (!gl_image_cell(image, cells, op0_addr, op0)) err |= TRACE_ERR_MISSING_CELL;
+        if (!gl_image_cell(image, cells, dst_addr, dst)) err |= TRACE_ERR_MISSING_CELL;
+        const u32 src = flag(2) + 2 * flag(3) + 4 * flag(4);
+        u64 base = 0;
+        if (src == 0) { if (op0 >> 32) err |= TRACE_ERR_NOT_AN_ADDRESS; base = op0; }      // (no address of a trace has more than 32 bits)
+        else if (src == 1) base = pc;
+        else if (src == 2) base = fp;
+        else if (src == 4) base = ap;
+        else err |= TRACE_ERR_BAD_OP1_SOURCE;
+        const u64 op1_addr = ((w >> 32) & 0xffff) + base - 0x8000;
+        if (!gl_image_cell(image, cells, op1_addr, op1)) err |= TRACE_ERR_MISSING_CELL;
+        const u32 pc_update = flag(7) + 2 * flag(8) + 4 * flag(9), res_logic = flag(5) + 2 * flag(6);
+        u64 res = 0;
+        if (pc_update == 4) { if (dst) res = gl_pow(dst, GL_P - 2); }                      // get_res of a conditional jump: dst^-1
+        else if (res_logic == 0) res = op1;
+        else if (res_logic == 1) res = gl_add(op0, op1);
+        else if (res_logic == 2) res = gl_mul(op0, op1);
+        else err |= TRACE_ERR_BAD_RES_LOGIC;
+        r.word = w; r.ap = gl_canon(ap); r.fp = gl_canon(fp);
+        r.addr[REC_PC] = sat32(pc); r.addr[REC_OP0] = sat32(op0_addr); r.addr[REC_DST] = sat32(dst_addr); r.addr[REC_OP1] = sat32(op1_addr);
+        r.jnz = flag(9);
+        r.val[REC_PC] = w; r.val[REC_OP0] = op0; r.val[REC_DST] = dst; r.val[REC_OP1] = op1;
+        r.res = res; r.tmp1 = r.jnz ? gl_mul(dst, res) : 0; r.mul = gl_mul(op0, op1);
+        if (err) gl_cpu_error(status, err, cyc);
+    }
+    __syncthreads();
+    const u64 live = num_cycles - cyc0 < CPU_CYC ? num_cycles - cyc0 : CPU_CYC;       // cycles of this workgroup
+    const u64 row0 = cyc0 * 16;
+    for (u32 it = 0; it < 16; ++it) {
+        const u32 lr = it * CPU_CYC + t, c = lr >> 4, o = lr & 15;
+        if (c >= live) break;
+        const GlCpuRec &r = rec[c];
+        flags[row0 + lr] = o == 15 ? 0 : (r.word >> (48 + o)) & ((1ull << (15 - o)) - 1);
+        {
+            u64 v = rc_fill;
+            if ((o & 3) == 0 && o != 12) v = (r.word >> (o == 0 ? 0 : o == 4 ? 32 : 16)) & 0xffff;       // off_dst, off_op1, off_op0 at 0, 4, 8
+            else if ((o & 3) == 3) v = o == 3 ? r.ap : o == 7 ? r.mul : o == 11 ? r.fp : r.res;
+            rc[row0 + lr] = v;
+        }
+        aux[row0 + lr] = o == 0 ? (r.jnz ? r.val[REC_DST] : 0) : o == 8 ? r.tmp1 : 0;
+        {
+            const u32 j = o >> 1, odd = o & 1;
+            u64 v;
+            if (j & 1) v = (j == 1 || j == 5) ? 0 : odd ? pad_value : 1;
+            else { const u32 k = j == 0 ? REC_PC : j == 2 ? REC_OP0 : j == 4 ? REC_DST : REC_OP1; v = odd ? r.val[k] : r.addr[k]; }
+            npc[row0 + lr] = v;
+        }
+    }
+    for (u32 it = 0; it < 8; ++it) {
+        const u32 lp = it * CPU_CYC + t, c = lp >> 3, j = lp & 7;
+        if (c >= live) break;
+        u32 a;
+        if (j & 1) a = (j == 1 || j == 5) ? 0u : 1u;
+        else a = rec[c].addr[j == 0 ? REC_PC : j == 2 ? REC_OP0 : j == 4 ? REC_DST : REC_OP1];
+        pool_addr[cyc0 * 8 + lp] = a;
+    }
+}
+
+// per cycle: its four ordered values at rows 4 j + 2 and ONE padding value at row 12 - every cycle, where the 252-bit layouts take one
+// on odd cycles (plain/trace.rs: RangeCheck::Unused has step CYCLE_HEIGHT); then rc_hi forever
+__global__ __launch_bounds__(256) void trace_gl64_rc_pool_kernel(TraceRcPlan p, const u32 *__restrict__ first, const uint16_t *__restrict__ padding, u64 num_cycles,
+                                                                 u64 *__restrict__ rc) {
+    const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (g < num_cycles * 4) rc[(g >> 2) * 16 + (g & 3) * 4 + 2] = run_value(first, p.rc_hi - p.rc_lo + 1, p.rc_lo, g, p.rc_hi);
+    else if (g < num_cycles * 5) { const u64 c = g - num_cycles * 4; rc[c * 16 + 12] = rc_padding(p, padding, p.pad0 + c); }
+}
+
+// the three kernels of the ordered memory that read or write cell values, over one-word cells (the others know addresses only)
+constexpr u32 GL_GAP_OFF = 14;               // Npc::GapAddr / GapVal: rows 14, 15 of a cycle
+__global__ __launch_bounds__(256) void mem_gap_fill_gl64_kernel(const u32 *__restrict__ gap_index, u32 cap, u64 num_cycles, u32 *__restrict__ count, u32 *__restrict__ rep,
+                                                                u64 *__restrict__ npc, u32 *__restrict__ pool_addr, u32 *status) {
+    const u32 a = blockIdx.x * 256 + threadIdx.x;
+    if (a > cap) return;
+    const u32 top = status[TRACE_ST_TOP], low = ~status[TRACE_ST_NLOW];
+    if (!(a > low && a < top && a >= 2 && count[a] == 0)) return;
+    const u32 g = gap_index[a];
+    if (g >= num_cycles) { status_error(status, TRACE_ERR_TOO_MANY_GAPS, a); return; }
+    const u64 row = (u64)g * 16 + GL_GAP_OFF;
+    npc[row] = a;
+    npc[row + 1] = 0;
+    pool_addr[row >> 1] = a;
+    count[a] = 1;
+    rep[a] = (u32)(row >> 1);
+}
+__device__ __forceinline__ u64 mem_value_of_gl64(u32 idx, u64 half, const u64 *npc, const u64 *pub_value) {
+    return idx < half ? npc[2 * (u64)idx + 1] : pub_value[idx - half];
+}
+__global__ __launch_bounds__(256) void mem_check_gl64_kernel(const u32 *__restrict__ pool_addr, u64 half, const u32 *__restrict__ pub_addr, u32 n_pub,
+                                                             const u64 *__restrict__ pub_value, u64 pad_value, const u32 *__restrict__ rep, const u64 *__restrict__ npc,
+                                                             u32 cap, u32 *status) {
+    const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= half + n_pub) return;
+    const u32 a = j < half ? pool_addr[j] : pub_addr[j - half];
+    if (a == 0 || a > cap) return;
+    const u64 mine = mem_value_of_gl64((u32)j, half, npc, pub_value);
+    const u64 want = a == 1 ? pad_value : mem_value_of_gl64(rep[a], half, npc, pub_value);
+    if (mine != want) status_error(status, TRACE_ERR_NOT_SINGLE_VALUED, a);
+}
+__global__ __launch_bounds__(256) void mem_fill_gl64_kernel(const u32 *__restrict__ start, u64 half, u32 cap, const u32 *__restrict__ rep, const u64 *__restrict__ npc,
+                                                            const u64 *__restrict__ pub_value, u64 pad_value, u64 *__restrict__ mem_col, u32 *status) {
+    const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= half) return;
+    u32 top = status[TRACE_ST_TOP];
+    if (top > cap) top = cap;
+    u64 av = 0, vv = 0;
+    if (j >= start[top + 1]) {                                       // the runs do not fill the column
+        status_error(status, TRACE_ERR_FILL, top);
+    } else {
+        u32 a = 0, b = top + 1;                                      // start[a] <= j < start[b]
+        while (b - a > 1) { const u32 m = (a + b) >> 1; if (start[m] <= j) a = m; else b = m; }
+        av = a;
+        vv = a <= 1 ? pad_value : mem_value_of_gl64(rep[a], half, npc, pub_value);
+    }
+    mem_col[2 * j] = av;
+    mem_col[2 * j + 1] = vv;
+}
+
 inline dim3 grid_for(u64 lanes, u32 block) { return dim3((u32)((lanes + block - 1) / block)); }
 
 }  // namespace
@@ -1160,6 +1341,47 @@ hipError_t launch_trace_ordered_memory(hipStream_t st, const TraceMemoryArgs &m,
     if ((e = exclusive_scan_u32(st, start, (u64)cap + 2, sums, nullptr)) != hipSuccess) return e;
     hipLaunchKernelGGL(mem_fill_total_kernel, dim3(1), dim3(64), 0, st, (const u32 *)start, half, cap, m.d_status);
     hipLaunchKernelGGL(mem_fill_kernel, grid_for(half, 256), dim3(256), 0, st, (const u32 *)start, half, cap, (const u32 *)rep, (const Fp *)m.npc, m.d_public_value,
+                       m.pad_value, m.memory, m.d_status);
+    return hipGetLastError();
+}
+
+// ---- the plain layout over the 64-bit field
+hipError_t launch_trace_gl64_memory_image(hipStream_t st, const u64 *d_records, u64 n_records, u64 *d_image, u64 cells) {
+    hipError_t e = hipMemsetAsync(d_image, 0xff, cells * 8, st);
+    if (e != hipSuccess || !n_records) return e;
+    hipLaunchKernelGGL(trace_gl64_memory_image_kernel, grid_for(n_records, 256), dim3(256), 0, st, d_records, n_records, d_image, cells);
+    return hipGetLastError();
+}
+hipError_t launch_trace_gl64_cpu(hipStream_t st, const u64 *d_states, u64 num_cycles, const u64 *d_image, u64 cells, u64 pad_value, u64 rc_fill, u64 *flags, u64 *npc,
+                                 u64 *rc, u64 *aux, u32 *d_pool_addr, u32 *d_status) {
+    hipLaunchKernelGGL(trace_gl64_cpu_kernel, grid_for(num_cycles, CPU_CYC), dim3(CPU_CYC), 0, st, d_states, num_cycles, d_image, cells, pad_value, rc_fill, flags, npc,
+                       rc, aux, d_pool_addr, d_status);
+    return hipGetLastError();
+}
+hipError_t launch_trace_gl64_rc_pool(hipStream_t st, const TraceRcPlan &p, const u32 *d_first, const uint16_t *d_padding, u64 num_cycles, u64 *rc) {
+    hipLaunchKernelGGL(trace_gl64_rc_pool_kernel, grid_for(num_cycles * 5, 256), dim3(256), 0, st, p, d_first, d_padding, num_cycles, rc);
+    return hipGetLastError();
+}
+// the pipeline of launch_trace_ordered_memory, kernel for kernel; scratch as there (trace_memory_scratch_words)
+hipError_t launch_trace_gl64_ordered_memory(hipStream_t st, const TraceGl64MemoryArgs &m, u32 *scratch) {
+    const u64 half = m.n / 2;
+    const u32 cap = (u32)half;
+    u32 *count = scratch, *rep = count + (cap + 2), *start = rep + (cap + 2), *sums = start + (cap + 2);
+    hipError_t e;
+    if ((e = hipMemsetAsync(count, 0, (size_t)(cap + 2) * 4, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(rep, 0xff, (size_t)(cap + 2) * 4, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(mem_count_kernel, grid_for(half, MEM_LANES * MEM_PER), dim3(MEM_LANES), 0, st, (const u32 *)m.d_pool_addr, half, cap, count, rep, m.d_status);
+    if (m.n_public) hipLaunchKernelGGL(mem_public_kernel, grid_for(m.n_public, 256), dim3(256), 0, st, m.d_public_addr, m.n_public, half, cap, count, rep, m.d_status);
+    hipLaunchKernelGGL(mem_gap_flags_kernel, grid_for((u64)cap + 1, 256), dim3(256), 0, st, (const u32 *)count, cap, (const u32 *)m.d_status, start);
+    if ((e = exclusive_scan_u32(st, start, (u64)cap + 1, sums, m.d_status + TRACE_ST_GAPS)) != hipSuccess) return e;
+    hipLaunchKernelGGL(mem_gap_fill_gl64_kernel, grid_for((u64)cap + 1, 256), dim3(256), 0, st, (const u32 *)start, cap, m.n / 16, count, rep, m.npc, m.d_pool_addr,
+                       m.d_status);
+    hipLaunchKernelGGL(mem_check_gl64_kernel, grid_for(half + m.n_public, 256), dim3(256), 0, st, (const u32 *)m.d_pool_addr, half, m.d_public_addr, m.n_public,
+                       m.d_public_value, m.pad_value, (const u32 *)rep, (const u64 *)m.npc, cap, m.d_status);
+    hipLaunchKernelGGL(mem_starts_kernel, grid_for((u64)cap + 2, 256), dim3(256), 0, st, (const u32 *)count, cap, m.n / 8, m.n_public, m.d_status, start);
+    if ((e = exclusive_scan_u32(st, start, (u64)cap + 2, sums, nullptr)) != hipSuccess) return e;
+    hipLaunchKernelGGL(mem_fill_total_kernel, dim3(1), dim3(64), 0, st, (const u32 *)start, half, cap, m.d_status);
+    hipLaunchKernelGGL(mem_fill_gl64_kernel, grid_for(half, 256), dim3(256), 0, st, (const u32 *)start, half, cap, (const u32 *)rep, (const u64 *)m.npc, m.d_public_value,
                        m.pad_value, m.memory, m.d_status);
     return hipGetLastError();
 }

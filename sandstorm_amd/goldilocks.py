@@ -545,6 +545,39 @@ def plain_extension_on_device(ctx, base_cols, challenges, check=True):
     return out, last_mem
 
 
+def plain_base_trace_on_device(ctx, trace_bin, memory_bin, pi, out=None):
+    """ExecutionTrace::new of the plain layout (layouts/src/plain/trace.rs:60-262; layouts/plain.py base_trace is the specification, cell
+    for cell) on the device, from the bytes of `trace.bin` and `memory.bin` (binary.write_register_states / write_memory) and the public
+    input: the files go up as they are - ~25 MB at 2^20 steps where the host-made columns are 671 MB - and csrc/trace.hip makes the cells
+    in HBM (hostlib.gl_base_trace_device).  -> the five base columns as torch int64 tensors on the device of ctx's stream (`out`: five
+    tensors of 16 * cycles values to write into).  What base_trace refuses is refused here with its message, as SandstormHipError"""
+    import torch
+    from . import hostlib
+    n = F.CYCLE_HEIGHT * (len(trace_bin) // 24)
+    if out is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        out = [torch.empty(n, dtype=torch.int64, device=dev) for _ in range(F.NUM_BASE_COLUMNS)]      # every cell is written by the kernels
+    if len(out) != F.NUM_BASE_COLUMNS or any(c.shape[0] != n or c.dtype != torch.int64 for c in out):
+        raise ValueError("five int64 columns of %d values" % n)
+    hostlib.gl_base_trace_device(ctx, trace_bin, memory_bin, pi, out)
+    return out
+
+
+def prove_files(ctx, trace_bin, memory_bin, pi, seed, options=None, out=None, want_times=False):
+    """the claim from the files in ONE call, what the reference's "Proof generated in" timer wraps (cli/src/main.rs:186-202): the base
+    columns made on the device, the extension column built and the proof written by the C++ host (hostlib.gl_prove_files); only the
+    plain AIR's lowering comes from Python.  -> the Proof Prover.prove writes from base_trace's columns with the same seed and statement
+    (with want_times: (Proof, {"trace_gen_s", "total_s"}))"""
+    import torch
+    from . import hostlib
+    n = F.CYCLE_HEIGHT * (len(trace_bin) // 24)
+    if out is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        out = [torch.empty(n, dtype=torch.int64, device=dev) for _ in range(F.NUM_BASE_COLUMNS)]
+    proof, times = hostlib.gl_prove_files(ctx, plain_air(), options or Options(), seed, trace_bin, memory_bin, pi, out)
+    return (proof, times) if want_times else proof
+
+
 # ---- the plain layout as an Air ------------------------------------------------------------------------------------------------
 def plain_air():
     """layouts/plain.py behind the Air interface; `statement` = its PublicInput"""

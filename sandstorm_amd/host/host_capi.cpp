@@ -18,6 +18,7 @@
 #include "trace_recursive.hpp"
 #include "trace_starknet.hpp"
 #include "device_trace.hpp"
+#include "trace_plain.hpp"
 #include "verifier.hpp"
 
 using namespace ssh;
@@ -705,11 +706,13 @@ int ssh_prove_files_device(ss_ctx *ctx, int layout, const uint8_t *trace_bin, ui
 typedef int (*ssh_gl_extension_cb)(void *user, const uint64_t *challenges, uint32_t nchallenges, uint64_t **d_cols_out);
 typedef int (*ssh_gl_program_cb)(void *user, const uint64_t *challenges, uint32_t nchallenges, const uint64_t *alpha, const uint64_t **blob_out,
                                  uint64_t *blob_len);
-int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base,
-                 uint32_t nbase, uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, ssh_gl_extension_cb ext_cb,
-                 ssh_gl_program_cb prog_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
-    try {
-        if (!ctx || !options || !seed || !statement_digest || !d_base || !mask || !prog_cb || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove: NULL argument");
+namespace {
+// the body ssh_gl_prove and ssh_gl_prove_files_device share: the proof for these columns as the u64 blob described above; `extension`
+// makes the extension trace's coordinate columns for the drawn challenges
+void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base, uint32_t nbase,
+                   uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, const gl::ExtensionBuilder &extension,
+                   ssh_gl_program_cb prog_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+    {
         gl::Options opt;
         opt.num_queries = options[0]; opt.log_blowup = options[1]; opt.grinding = options[2]; opt.fold = options[3]; opt.max_remainder = options[4];
         opt.sha256 = options[5] != 0;
@@ -720,13 +723,7 @@ int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32],
         std::vector<std::pair<uint32_t, uint32_t>> cells;
         for (uint32_t j = 0; j < nmask; ++j) cells.push_back({mask[2 * j], mask[2 * j + 1]});
         auto flat = [](const std::vector<gl::Fq3> &v) { std::vector<uint64_t> o; for (auto &c : v) o.insert(o.end(), c.begin(), c.end()); return o; };
-        const gl::Proof p = gl::prove(ctx, opt, sd, st, base, n, cells, num_challenges, num_ext,
-            [&](const std::vector<gl::Fq3> &ch) {
-                std::vector<uint64_t *> cols(num_ext, nullptr);
-                const std::vector<uint64_t> f = flat(ch);
-                if (!ext_cb || ext_cb(user, f.data(), (uint32_t)ch.size(), cols.data()) != 0) throw std::runtime_error("extension callback failed");
-                return std::vector<const uint64_t *>(cols.begin(), cols.end());
-            },
+        const gl::Proof p = gl::prove(ctx, opt, sd, st, base, n, cells, num_challenges, num_ext, extension,
             [&](const std::vector<gl::Fq3> &ch, const gl::Fq3 &alpha) {
                 const uint64_t *blob = nullptr;
                 uint64_t len = 0;
@@ -765,6 +762,82 @@ int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32],
         *proof_blob = (uint64_t *)malloc(out.size() * 8);
         memcpy(*proof_blob, out.data(), out.size() * 8);
         *proof_len = out.size();
+    }
+}
+}  // namespace
+int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base,
+                 uint32_t nbase, uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, ssh_gl_extension_cb ext_cb,
+                 ssh_gl_program_cb prog_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+    try {
+        if (!ctx || !options || !seed || !statement_digest || !d_base || !mask || !prog_cb || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove: NULL argument");
+        gl_prove_blob(ctx, options, seed, statement_digest, d_base, nbase, n, mask, nmask, num_challenges, num_ext,
+            [&](const std::vector<gl::Fq3> &ch) {
+                std::vector<uint64_t *> cols(num_ext, nullptr);
+                std::vector<uint64_t> f;
+                for (auto &c : ch) f.insert(f.end(), c.begin(), c.end());
+                if (!ext_cb || ext_cb(user, f.data(), (uint32_t)ch.size(), cols.data()) != 0) throw std::runtime_error("extension callback failed");
+                return std::vector<const uint64_t *>(cols.begin(), cols.end());
+            }, prog_cb, user, proof_blob, proof_len);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+
+// ---- the 64-bit field's claim FROM THE FILES (cli/src/main.rs:186-202 wraps ExecutionTrace::new, layouts/src/plain/trace.rs:60-262, inside its
+// "Proof generated in" timer).  ssh_gl_base_trace_device: trace.bin / memory.bin and the public memory (one u64 per address and per value)
+// -> the plain layout's five base columns in d_cols (16 * n_steps u64 each: flags, pool, ordered memory, range check, auxiliary), made in
+// HBM by csrc/trace.hip (host/trace_plain.cpp: the plan and the driver); final when the call returns; the input's errors are
+// layouts/plain.py base_trace's refusals.
+int ssh_gl_base_trace_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len, uint64_t n_steps,
+                             const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint64_t *const d_cols[5]) {
+    try {
+        plain_base_trace_device(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// what the last generation on the calling thread (ssh_gl_base_trace_device, ssh_gl_prove_files_device) uploaded: out = {bytes}
+int ssh_gl_trace_last_stats(uint64_t out[1]) {
+    if (!out) { g_err = "ssh_gl_trace_last_stats: NULL argument"; return 1; }
+    out[0] = plain_trace_stats().bytes_uploaded;
+    return 0;
+}
+// files -> proof in one call: the columns as above, then the extension column made HERE (Trace::build_extension_columns,
+// plain/trace.rs:274-330: the memory and the range-check running quotients, two ss_running_product_gl64x3 calls - what
+// goldilocks.plain_extension_on_device does; refused if the range-check product does not close), then ssh_gl_prove's proof blob.  The
+// composition program still comes through prog_cb (the plain AIR is lowered in Python); mask as for ssh_gl_prove.  times_out (optional,
+// 2 doubles) as ssh_prove_files_device: until the columns were final, and the whole call.
+int ssh_gl_prove_files_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len, uint64_t n_steps,
+                              const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint64_t *const d_cols[5], const uint32_t options[6],
+                              const uint8_t seed[32], const uint8_t statement_digest[32], const uint32_t *mask, uint32_t nmask, ssh_gl_program_cb prog_cb, void *user,
+                              double *times_out, uint64_t **proof_blob, uint64_t *proof_len) {
+    struct Columns {                                                 // the extension trace's three coordinate columns: this call's own
+        ss_ctx *ctx; uint64_t *col[3] = {nullptr, nullptr, nullptr};
+        ~Columns() { (void)ss_ctx_sync(ctx); for (auto *c : col) if (c) (void)ss_dev_free(ctx, c); }
+    };
+    try {
+        if (!ctx || !options || !seed || !statement_digest || !d_cols || !mask || !prog_cb || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove_files_device: NULL argument");
+        const auto t_start = std::chrono::steady_clock::now();
+        plain_base_trace_device(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols);
+        const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+        const uint64_t n = 16 * n_steps;
+        enum { NPC = 1, MEMORY = 2, RANGE_CHECK = 3 };
+        Columns ext{ctx};
+        auto ok = [](ss_status st) { if (st != SS_OK) throw std::runtime_error(ss_last_error()); };
+        gl_prove_blob(ctx, options, seed, statement_digest, d_cols, 5, n, mask, nmask, 3, 3,
+            [&](const std::vector<gl::Fq3> &ch) {
+                if (ch.size() != 3) throw std::runtime_error("the plain layout draws three challenges");
+                for (auto *&c : ext.col) {
+                    if (!c) { void *p = nullptr; ok(ss_dev_alloc(ctx, n * 8, &p)); c = (uint64_t *)p; }
+                    ok(ss_dev_zero(ctx, c, n * 8));                   // (rows 3 mod 4 belong to neither product)
+                }
+                const uint64_t *npc = d_cols[NPC], *mem = d_cols[MEMORY], *rc = d_cols[RANGE_CHECK];
+                uint64_t last_rc[3];
+                ok(ss_running_product_gl64x3(ctx, npc, npc + 1, mem, mem + 1, 2, n / 2, ch[0].data(), ch[1].data(), ext.col, 2, 0, nullptr));
+                ok(ss_running_product_gl64x3(ctx, rc, nullptr, rc + 2, nullptr, 4, n / 4, ch[2].data(), nullptr, ext.col, 4, 1, last_rc));
+                if (last_rc[0] != 1 || last_rc[1] || last_rc[2]) throw std::runtime_error("the range-check permutation does not close");
+                return std::vector<const uint64_t *>(ext.col, ext.col + 3);
+            }, prog_cb, user, proof_blob, proof_len);
+        if (ss_ctx_sync(ctx) != SS_OK) throw std::runtime_error(ss_last_error());
+        if (times_out) { times_out[0] = gen_s; times_out[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }

@@ -498,30 +498,10 @@ GL_EXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, 
 GL_PROG_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64))
 
 
-def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, statement=None):
-    """the 64-bit field's claim by the C++ host (host/goldilocks_prover.cpp ssh_gl_prove; the mirror of goldilocks.Prover.prove, which
-    writes the same proof arrays): every stage a kernel behind the C ABI, the transcript in C++; what the LAYOUT decides comes from here
-    through two callbacks - the extension trace's coordinate columns for the drawn challenges (build_extension, as goldilocks.Prover
-    takes it) and the lowered composition program for them (air.composition + air_program.lower).  air: a goldilocks.Air; base_cols:
-    device columns of n values.  -> goldilocks.Proof"""
+def _gl_program_callback(ctx, air, n, tables, statement, keep):
+    """ssh_gl_program_cb for a goldilocks.Air: the lowered composition program for the drawn challenges (air.composition +
+    air_program.lower) as the blob host_capi.cpp documents; what it allocates stays in `keep`"""
     from . import air_program as ap, goldilocks as gs
-    opt = options or gs.Options()
-    n = int(base_cols[0].shape[0]) if hasattr(base_cols[0], "shape") else int(base_cols[0].nbytes // 8)
-    tables = tables or air.make_tables(n, opt.log_blowup)
-    keep = []
-
-    def ext_cb(_user, ch_ptr, nch, out_ptr):
-        try:
-            ch = [tuple(int(ch_ptr[3 * i + k]) for k in range(3)) for i in range(nch)]
-            cols = list(build_extension(ch))
-            keep.append(cols)
-            for i, col in enumerate(cols):
-                out_ptr[i] = be._ptr_of(col)
-            return 0
-        except Exception:                       # never let an exception cross the C boundary
-            import traceback
-            traceback.print_exc()
-            return 1
 
     def prog_cb(_user, ch_ptr, nch, alpha_ptr, blob_out, len_out):
         try:
@@ -544,6 +524,34 @@ def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, s
             import traceback
             traceback.print_exc()
             return 1
+    return GL_PROG_CB(prog_cb)
+
+
+def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, statement=None):
+    """the 64-bit field's claim by the C++ host (host/goldilocks_prover.cpp ssh_gl_prove; the mirror of goldilocks.Prover.prove, which
+    writes the same proof arrays): every stage a kernel behind the C ABI, the transcript in C++; what the LAYOUT decides comes from here
+    through two callbacks - the extension trace's coordinate columns for the drawn challenges (build_extension, as goldilocks.Prover
+    takes it) and the lowered composition program for them (air.composition + air_program.lower).  air: a goldilocks.Air; base_cols:
+    device columns of n values.  -> goldilocks.Proof"""
+    from . import goldilocks as gs
+    opt = options or gs.Options()
+    n = int(base_cols[0].shape[0]) if hasattr(base_cols[0], "shape") else int(base_cols[0].nbytes // 8)
+    tables = tables or air.make_tables(n, opt.log_blowup)
+    keep = []
+
+    def ext_cb(_user, ch_ptr, nch, out_ptr):
+        try:
+            ch = [tuple(int(ch_ptr[3 * i + k]) for k in range(3)) for i in range(nch)]
+            cols = list(build_extension(ch))
+            keep.append(cols)
+            for i, col in enumerate(cols):
+                out_ptr[i] = be._ptr_of(col)
+            return 0
+        except Exception:                       # never let an exception cross the C boundary
+            import traceback
+            traceback.print_exc()
+            return 1
+
     h = load()
     h.ssh_gl_prove.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32),
                                C.c_uint32, C.c_uint32, C.c_uint32, GL_EXT_CB, GL_PROG_CB, C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
@@ -551,11 +559,17 @@ def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, s
     mask = np.ascontiguousarray([v for cell in air.mask for v in cell], dtype=np.uint32)
     out, ln = C.POINTER(C.c_uint64)(), C.c_uint64()
     _check(h.ssh_gl_prove(ctx.handle, opts, bytes(seed), gs.statement_digest(statement), be._ptr_array(base_cols), len(base_cols), n,
-                          mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask), air.num_challenges, air.num_ext, GL_EXT_CB(ext_cb), GL_PROG_CB(prog_cb), None,
+                          mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask), air.num_challenges, air.num_ext, GL_EXT_CB(ext_cb), _gl_program_callback(ctx, air, n, tables, statement, keep), None,
                           C.byref(out), C.byref(ln)))
     w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
     h.ssh_free(out)
     del keep[:]
+    return _gl_proof_of_blob(w, opt)
+
+
+def _gl_proof_of_blob(w, opt):
+    """the u64 proof blob of ssh_gl_prove / ssh_gl_prove_files_device (host_capi.cpp) -> goldilocks.Proof"""
+    from . import goldilocks as gs
     o = 0
 
     def take(k):
@@ -587,6 +601,72 @@ def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, s
         fl.opening = opening()
     assert o == len(w)
     return proof
+
+
+def _gl_files_args(trace_bin, memory_bin, pi):
+    """the arguments ssh_gl_base_trace_device / ssh_gl_prove_files_device share: the files' bytes, the step count, the public memory as
+    one u64 per address and per value; -> (args, keep-alive)"""
+    if len(trace_bin) % 24:
+        raise _lib.SandstormHipError("host: trace file is not a sequence of (ap, fp, pc) u64 triples")
+    addrs = np.array([a for a, _ in pi.public_memory], dtype=np.uint64)
+    vals = np.array([int(v) % (2**64 - 2**32 + 1) for _, v in pi.public_memory], dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    return (bytes(trace_bin), len(trace_bin), bytes(memory_bin), len(memory_bin), len(trace_bin) // 24, addrs.ctypes.data_as(u64p), vals.ctypes.data_as(u64p),
+            len(addrs)), (addrs, vals)
+
+
+_GL_FILES_ARGTYPES = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64]
+
+
+def gl_base_trace_device(ctx, trace_bin: bytes, memory_bin: bytes, pi, dev_cols):
+    """the plain layout's five base columns over the 64-bit field made ON the device from the raw files (host_capi.cpp
+    ssh_gl_base_trace_device -> host/trace_plain.cpp -> csrc/trace.hip): trace.bin / memory.bin go up as they are.  dev_cols: five device
+    columns of 16 * cycles u64 (DeviceBuffers, torch tensors or addresses), final when the call returns.  The input's errors are
+    layouts/plain.py base_trace's refusals, raised as SandstormHipError"""
+    if len(dev_cols) != 5:
+        raise _lib.SandstormHipError("host: %d device columns for a layout of 5" % len(dev_cols))
+    args, keep = _gl_files_args(trace_bin, memory_bin, pi)
+    fn = load().ssh_gl_base_trace_device
+    fn.argtypes = [C.c_void_p] + _GL_FILES_ARGTYPES + [C.POINTER(C.c_void_p)]
+    _check(fn(ctx.handle if ctx is not None else None, *args, be._ptr_array(dev_cols)))
+    del keep
+    return dev_cols
+
+
+def gl_trace_last_stats():
+    """what the last generation on this thread (gl_base_trace_device, gl_prove_files) uploaded (host_capi.cpp ssh_gl_trace_last_stats)
+    -> {"bytes_uploaded"}"""
+    out = (C.c_uint64 * 1)()
+    fn = load().ssh_gl_trace_last_stats
+    fn.argtypes = [C.POINTER(C.c_uint64)]
+    _check(fn(out))
+    return {"bytes_uploaded": int(out[0])}
+
+
+def gl_prove_files(ctx, air, options, seed, trace_bin: bytes, memory_bin: bytes, pi, dev_cols, tables=None):
+    """the 64-bit field's claim from the files in one call (host_capi.cpp ssh_gl_prove_files_device): the base columns made on the device
+    in `dev_cols`, the extension column built by the C++ host, then gl_prove's proof; the composition program comes from here
+    (air.composition for the statement `pi`).  -> (goldilocks.Proof, {"trace_gen_s", "total_s"})"""
+    from . import goldilocks as gs
+    opt = options or gs.Options()
+    if len(dev_cols) != 5:
+        raise _lib.SandstormHipError("host: %d device columns for a layout of 5" % len(dev_cols))
+    n = 16 * (len(trace_bin) // 24)
+    tables = tables or air.make_tables(n, opt.log_blowup)
+    keep = []
+    args, keep_args = _gl_files_args(trace_bin, memory_bin, pi)
+    fn = load().ssh_gl_prove_files_device
+    fn.argtypes = [C.c_void_p] + _GL_FILES_ARGTYPES + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, GL_PROG_CB,
+                                                       C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    opts = (C.c_uint32 * 6)(opt.num_queries, opt.log_blowup, opt.grinding, opt.fold, opt.max_remainder, 1 if opt.hash == "sha256" else 0)
+    mask = np.ascontiguousarray([v for cell in air.mask for v in cell], dtype=np.uint32)
+    out, ln, times = C.POINTER(C.c_uint64)(), C.c_uint64(), (C.c_double * 2)()
+    _check(fn(ctx.handle, *args, be._ptr_array(dev_cols), opts, bytes(seed), gs.statement_digest(pi), mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask),
+              _gl_program_callback(ctx, air, n, tables, pi, keep), None, times, C.byref(out), C.byref(ln)))
+    w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
+    load().ssh_free(out)
+    del keep[:], keep_args
+    return _gl_proof_of_blob(w, opt), {"trace_gen_s": times[0], "total_s": times[1]}
 
 
 _INSTANCE_SHAPES = (("pedersen", 9), ("range_check", 5), ("ecdsa", 17), ("bitwise", 9), ("ec_op", 21), ("poseidon", 13))
