@@ -2434,10 +2434,11 @@ const QGenKernel *quotient_gen_find(const uint32_t *code, uint32_t n_instr, bool
     return nullptr;
 }
 
-// row0 / npoints / block: the whole domain (0, N, false) or a row block whose columns carry the rows behind it
+// row0 / npoints / block_rows: the whole domain (0, N, 0) or a row block whose columns carry the rows behind it (block_rows each)
 ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_air_program *prog, const uint64_t *const *d_lde_cols,
                                  uint32_t ncols, uint32_t log_N, uint32_t log_blowup, const uint64_t offset[4], uint64_t *d_out,
-                                 uint64_t row0, uint64_t npoints, bool block) {
+                                 uint64_t row0, uint64_t npoints, uint64_t block_rows) {
+    const bool block = block_rows != 0;
     const uint64_t N = npoints;
     // constants in limb form: 9 x 28-bit limbs of the interchange image (add / sub / mov) and of the R280 form (fl_mul_r280)
     const uint32_t nc = prog->n_consts ? prog->n_consts : 1u;
@@ -2487,7 +2488,22 @@ ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_ai
         for (int j = 0; j < 8; ++j) host[wstep_at + 8 * (size_t)p + j] = ws.v[j];
     }
     const size_t scaled_at = ((host.size() * 4 + 256 + 63) / 64) * 64;
-    ss_status st = ctx->ensure_scratch(scaled_at + scaled_felts * sizeof(Fp));
+    // the derived columns (quotient_derive.h) behind the scaled tables.  On the whole domain a column has N rows and wraps with the
+    // mask, as the cells it replaces do; on a row block it has the rows the caller's columns carry less its terms' reach - every row
+    // the kernels read, since the program reads the source column as far (eval_quotient_impl checked that against block_rows)
+    if (gen.n_derived > (uint32_t)QG_MAX_DERIVED) return fail(SS_ERR_UNSUPPORTED, "%u derived columns > %d", gen.n_derived, QG_MAX_DERIVED);
+    size_t derived_at[QG_MAX_DERIVED] = {}, scratch_end = ((scaled_at + scaled_felts * sizeof(Fp) + 63) / 64) * 64;
+    uint64_t derived_rows[QG_MAX_DERIVED] = {};
+    for (uint32_t j = 0; j < gen.n_derived; ++j) {
+        const QGenDerived &d = gen.derived[j];
+        const uint64_t reach = (uint64_t)qg_derived_reach(d) << log_blowup;
+        if (d.col >= ncols || d.n_terms == 0 || d.n_terms > (uint32_t)QG_MAX_DERIVED_TERMS) return fail(SS_ERR_INVALID, "derived column %u of column %u", j, d.col);
+        if (block && block_rows <= reach) return fail(SS_ERR_INVALID, "derived column %u reaches beyond the block's %llu rows", j, (unsigned long long)block_rows);
+        derived_rows[j] = block ? block_rows - reach : N;
+        derived_at[j] = scratch_end;
+        scratch_end += ((size_t)derived_rows[j] * sizeof(Fp) + 63) / 64 * 64;
+    }
+    ss_status st = ctx->ensure_scratch(scratch_end);
     if (st != SS_OK) return st;
     hipStream_t s = ctx->stream;
     void *pinned = nullptr;                      // no host round trip: the copy leaves from pinned memory the context owns
@@ -2509,6 +2525,14 @@ ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_ai
     a.sink = (Fp *)((char *)ctx->scratch + ((host.size() * 4 + 63) / 64) * 64);      // inside ensure_scratch's 256 spare bytes
     a.npoints = npoints; a.row0 = (uint32_t)row0; a.log_blowup = log_blowup;
     a.trace_mask = block ? 0xffffffffu : (uint32_t)((1ull << log_N) - 1ull);
+    // built at every call, in front of the first part: the source column's contents change from proof to proof
+    for (int j = 0; j < QG_MAX_DERIVED; ++j) a.derived[j] = nullptr;
+    for (uint32_t j = 0; j < gen.n_derived; ++j) {
+        Fp *out = (Fp *)((char *)ctx->scratch + derived_at[j]);
+        ss_ctx::Scope prof(ctx, SS_PROF_QUOTIENT);
+        HIP_TRY(launch_qg_derive_column(s, gen.derived[j], (const Fp *)d_lde_cols[gen.derived[j].col], out, derived_rows[j], log_blowup, a.trace_mask));
+        a.derived[j] = out;
+    }
     a.w = w_dom;
     a.offset = fp_mul(offset ? fp_from_limbs64(offset) : fp_one(), fp_pow_u64(a.w, row0));
     // the program's parts, one launch each on the context's stream: part 0 stores its sum, the others add theirs (a lane owns the
@@ -2567,7 +2591,7 @@ static ss_status eval_quotient_impl(ss_ctx *ctx, const ss_air_program *prog, con
         const QGenKernel *gen = quotient_gen_find(prog->code, prog->n_instr, &variant_missing);
         if (!gen && variant_missing) return fail(SS_ERR_UNSUPPORTED, "SS_QG_VARIANT names a kernel variant this build does not hold (make QG_AB=1)");
         if (gen && gen->n_consts == prog->n_consts && gen->n_tables == prog->n_tables && gen->ncols <= ncols)
-            return eval_quotient_compiled(ctx, *gen, prog, d_lde_cols, ncols, log_N, log_blowup, offset, d_out, row0, N, block);
+            return eval_quotient_compiled(ctx, *gen, prog, d_lde_cols, ncols, log_N, log_blowup, offset, d_out, row0, N, block ? block_rows : 0);
     }
     return eval_quotient_interpreted(ctx, prog, d_lde_cols, ncols, log_N, log_blowup, offset, row0, N, block, d_out);
 }

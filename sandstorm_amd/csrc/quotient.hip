@@ -266,4 +266,18 @@ hipError_t launch_qg_scale_tables(hipStream_t st, const QgScaleArgs &a, uint64_t
     return hipGetLastError();
 }
 
+// ---- a derived column of the compiled kernels (quotient_derive.h): one lane per row, a streaming pass (16-byte loads of the
+// source column's cells, 16-byte stores) queued in front of the kernels that read it
+__global__ __launch_bounds__(256) void qg_derive_column_kernel(QGenDerived d, const Fp *col, Fp *out, uint64_t rows, uint32_t log_blowup, uint32_t trace_mask) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k >= rows) return;
+    qg_store(out + k, qg_derived_row(d, (uint32_t)k, log_blowup, trace_mask, [col](uint32_t index) { return qg_load_raw(col, index); }));
+}
+
+hipError_t launch_qg_derive_column(hipStream_t st, const QGenDerived &d, const Fp *col, Fp *out, uint64_t rows, uint32_t log_blowup, uint32_t trace_mask) {
+    if (rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(qg_derive_column_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, d, col, out, rows, log_blowup, trace_mask);
+    return hipGetLastError();
+}
+
 }  // namespace ss

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include "fp252.h"
 #include "fl252.h"
+#include "quotient_derive.h"
 
 namespace ss {
 
@@ -34,6 +35,7 @@ struct QGenArgs {
     uint32_t row0;                               // global row of local point 0 (tables are indexed by the global row)
     uint32_t trace_mask;                         // trace cells are read at (k + shift) & trace_mask: N - 1 on whole columns, ~0 on a
     uint32_t log_blowup;                         // row block that carries the rows behind it (ss_eval_quotient_rows)
+    const Fp *derived[QG_MAX_DERIVED];           // the derived columns (quotient_derive.h; made per launch), indexed like the trace columns
 };
 
 // One compiled program = one or more kernels ("parts", tools/gen_quotient.py split_program) whose outputs sum to the
@@ -55,6 +57,8 @@ struct QGenKernel {
     QGenPart parts[QG_MAX_PARTS];
     uint32_t n_scaled;                           // tables the kernels read from a 2^24-fold copy (multiplier-only tables): their numbers;
     const uint32_t *scaled;                      // copy j is addressed by descriptor n_tables + j
+    uint32_t n_derived;                          // derived columns the kernels read through QG_DERIVED_RAW (quotient_derive.h)
+    QGenDerived derived[QG_MAX_DERIVED];
 };
 
 // the launch's copy of the multiplier-only tables times 2^24 (csrc/quotient.hip qg_scale_tables_kernel)
@@ -65,6 +69,9 @@ struct QgScaleArgs {
     uint32_t n, src[QG_MAX_SCALED], dst[QG_MAX_SCALED], len[QG_MAX_SCALED];      // per table: first element in `tables`, in `out`, elements
 };
 hipError_t launch_qg_scale_tables(hipStream_t st, const QgScaleArgs &a, uint64_t total_felts);
+// rows 0 .. rows - 1 of a derived column of `col` (csrc/quotient.hip qg_derive_column_kernel): the caller guarantees that
+// (k + (off << log_blowup)) & trace_mask lies inside `col` for every k < rows and every term's offset
+hipError_t launch_qg_derive_column(hipStream_t st, const QGenDerived &d, const Fp *col, Fp *out, uint64_t rows, uint32_t log_blowup, uint32_t trace_mask);
 
 #define QG_VARIANT(entry) const QGenKernel &entry();
 #include "quotient_gen_variants.inc"             // quotient_gen_starknet(), quotient_gen_recursive() [, the A/B variants]
@@ -130,6 +137,7 @@ __device__ __forceinline__ void qg_wide_tail(QgWide &w, const Fl &l) {
 // operands (the generator writes these with immediates).  `idx` is the point's local index: this point's, or the next
 // point's for the loads issued across the loop edge.
 #define QG_TRACE_RAW(col, off, idx) qg_load_raw(a.cols[col], ((idx) + ((off) << lb)) & maskN)
+#define QG_DERIVED_RAW(d, off, idx) qg_load_raw(a.derived[d], ((idx) + ((off) << lb)) & maskN)
 #define QG_TABLE_RAW(t, idx) qg_load_raw(a.tables + tdesc[2 * (t)], ((idx) + row0) & tdesc[2 * (t) + 1])
 #define QG_TABLE_SCALED_RAW(t, idx) qg_load_raw(a.tables_scaled + tdesc[2 * (t)], ((idx) + row0) & tdesc[2 * (t) + 1])
 #define QG_CONST(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k))

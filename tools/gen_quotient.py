@@ -234,19 +234,74 @@ def compact_slots(ins):
 
 
 TEMP_ACC = 4            # a fifth accumulator the generator may use (the program format has four)
+SRC_DERIVED = 6         # an operand kind of the generator's own (the program format has six): a cell of a DERIVED COLUMN,
+                        # w1 = (derived column << 24) | row offset - see derived_column_of
+MAX_DERIVED = 2         # derived columns per layout (each costs the launch one column of scratch and one streaming pass)
+# ... and the loads a column has to save per point to be given that pass and that memory.  Measured (2^25 points,
+# profiles/quotient_derived_flag_column.json): the flag column saves 100 loads per point and 4.0 ms of starknet's first part for a
+# 0.37 ms pass and N felts of the context's scratch (1 GB there).  The recursive layout's other candidate (column 6, cell - 2 x (cell
+# four rows on): 9 uses, 18 loads saved) measured 1.2 ms off its kernel for a second 0.38 ms pass - 0.8 ms net, 0.4 % of a proof -
+# and a second gigabyte: below this floor it stays rematerialised.  The floor is that trade, set between the two; lower it to take it.
+MIN_DERIVED_LOADS_SAVED = 32
 
 
-def rematerialize_cheap_slots(ins, max_recipe=4):
+def derived_column_of(recipe):
+    """A recipe (rematerialize_cheap_slots) whose operands are cells of ONE trace column is a fixed integer combination of that
+    column's rows: sum_t coefficient_t x column[row + offset_t].  Recipes that agree up to a common row shift read the same
+    DERIVED COLUMN F[i] = sum_t coefficient_t x column[i + (offset_t - base) << log_blowup] at different rows - the 16 decoded flags
+    of the CPU constraints, cell_j - 2 cell_(j+1), are F = column 0 - 2 x (column 0, one row on) at row offsets 0 .. 15.
+    -> ((column, ((offset - base, coefficient), ...)), base), or None (a constant among the operands, two columns, all cancelled)"""
+    coef = {}
+    for op, _, kind, w1 in recipe:
+        if kind != SRC_TRACE:
+            return None
+        if op == OP_MOV:
+            coef = {}
+        elif op == OP_RSUB:
+            coef = {k: -c for k, c in coef.items()}
+        coef[w1] = coef.get(w1, 0) + (-1 if op == OP_SUB else 1)
+    terms = {w1 & 0xffffff: c for w1, c in coef.items() if c}
+    if len(set(w1 >> 24 for w1 in coef)) != 1 or not terms:
+        return None
+    base = min(terms)
+    return (next(iter(coef)) >> 24, tuple(sorted((off - base, c) for off, c in terms.items()))), base
+
+
+def choose_derived_columns(found, max_columns=MAX_DERIVED, min_saved=None):
+    """found: derived column -> [reads per point, loads saved per point] (rematerialize_cheap_slots over every part that
+    rematerialises).  A column nobody reads twice, or that saves fewer than MIN_DERIVED_LOADS_SAVED loads, is not worth its pass; of the
+    others the ones that save the most loads."""
+    min_saved = MIN_DERIVED_LOADS_SAVED if min_saved is None else min_saved
+    keep = sorted((-saved, key) for key, (reads, saved) in found.items() if reads >= 2 and saved >= min_saved)
+    return [key for _, key in keep[:max_columns]]
+
+
+def rematerialize_cheap_slots(ins, max_recipe=4, derived=(), found=None):
     """Scratch values that are a few additions of trace cells (the 16 decoded flags of the CPU constraints: cell - 2 x next cell)
     need not sit in a slot from their definition to their last use - 17 of them at once keep the starknet program's first part
     at one wave per SIMD (139 KB of LDS per 256 lanes).  Such a value is recomputed where it is read: its defining instructions
     (a MOV from a trace cell / constant followed by ADD / SUB / RSUB of cells or constants, at most `max_recipe` instructions) are
-    replayed into a fifth accumulator in front of the reading instruction, and its store disappears.  -> program"""
+    replayed into a fifth accumulator in front of the reading instruction, and its store disappears.  -> program
+
+    `derived`: the layout's derived columns (derived_column_of, choose_derived_columns).  A recipe that is a row of one of them is
+    not recomputed at all: every read of it is ONE load of that column (operand kind SRC_DERIVED), and so is its definition where
+    the defining instructions stand together (they and the store disappear).  The loaded value is a cell like any other: canonical,
+    bound 1.  `found`, if given, collects per derived column the reads and the loads a point would save."""
     leafy = lambda kind: kind in (SRC_TRACE, SRC_CONST)
     recipe = [None] * 4                            # per accumulator: the instructions that made its value, if they qualify
     slot_recipe, out = {}, []
     for op, d, kind, w1 in ins:
         if op <= OP_MUL and kind == SRC_SLOT and w1 in slot_recipe:
+            col = derived_column_of(slot_recipe[w1])
+            if col is not None and found is not None:
+                found.setdefault(col[0], [0, 0])
+                found[col[0]][0] += 1
+                found[col[0]][1] += len(slot_recipe[w1]) - 1
+            if col is not None and col[0] in derived:
+                out.append((op, d, SRC_DERIVED, (list(derived).index(col[0]) << 24) | col[1]))
+                if d < 4:
+                    recipe[d] = None
+                continue
             for rop, _, rkind, rw1 in slot_recipe[w1]:
                 out.append((rop, TEMP_ACC, rkind, rw1))
             out.append((op, d, SRC_ACC, TEMP_ACC))
@@ -256,6 +311,12 @@ def rematerialize_cheap_slots(ins, max_recipe=4):
         if op == OP_ST:
             if recipe[d] is not None and len(recipe[d]) <= max_recipe:
                 slot_recipe[w1] = list(recipe[d])  # no store: every read below recomputes
+                col = derived_column_of(recipe[d])
+                if col is not None and out[-len(recipe[d]):] == recipe[d]:      # the definition itself: one load as well
+                    if found is not None:
+                        found.setdefault(col[0], [0, 0])[1] += len(recipe[d]) - 1
+                    if col[0] in derived:
+                        out[-len(recipe[d]):] = [(OP_MOV, d, SRC_DERIVED, (list(derived).index(col[0]) << 24) | col[1])]
                 continue
             slot_recipe.pop(w1, None)
             out.append((op, d, kind, w1))
@@ -351,12 +412,22 @@ def generate(layout, all_variants=False):
             full_length = {t for t, spec in enumerate(template_program.specs[layout]) if spec[0] == "inverse"}
             scaled = sorted(t for t, ops in uses.items() if ops == {OP_MUL} and t not in full_length)
         names = []
-        for j, (part, cfg) in enumerate(zip(parts, cfgs)):
+        # the parts that rematerialise (the decoded flags: recomputed at their uses instead of parked, 17 -> 6 slots) - and what of
+        # that is a row of a derived column, read instead of recomputed (one list per layout: the launch builds the columns once)
+        compacted = [compact_slots(part) for part in parts]
+        remat_here = [remat and part_slots > REMAT_ABOVE_SLOTS for _, part_slots in compacted]
+        derived = []
+        if DERIVED_COLUMNS:
+            found = {}
+            for (part, _), here in zip(compacted, remat_here):
+                if here:
+                    rematerialize_cheap_slots(part, found=found)
+            derived = choose_derived_columns(found)
+        for j, ((part, part_slots), cfg) in enumerate(zip(compacted, cfgs)):
             depth, slots_in_regs, wgs, fence, fuse, threads = cfg[:6]
             sync = int(os.environ.get("QG_SYNC", cfg[6] if len(cfg) > 6 else 0))
-            part, part_slots = compact_slots(part)
-            if remat and part_slots > REMAT_ABOVE_SLOTS:     # the decoded flags: recomputed at their uses instead of parked (17 -> 6 slots)
-                part, part_slots = compact_slots(rematerialize_cheap_slots(part))
+            if remat_here[j]:
+                part, part_slots = compact_slots(rematerialize_cheap_slots(part, derived=derived))
             if not slots_in_regs:
                 lds = part_slots * 2 * threads * 16 + n_consts * 36 * 4
                 assert lds * wgs <= LDS_BYTES_PER_CU, "%s%s part %d: %d slots + constants = %d B of LDS x %d workgroups per CU" % (layout, suffix, j, part_slots, lds, wgs)
@@ -369,10 +440,10 @@ def generate(layout, all_variants=False):
             lazy_sub = os.environ["QG_SUB_LAZY2"] != "0" if "QG_SUB_LAZY2" in os.environ else lazy_sub
             const_factor = os.environ["QG_CONST_FACTOR"] != "0" if "QG_CONST_FACTOR" in os.environ else const_factor
             body = generate_body(layout, part, n_consts, part_slots, n_tables, ncols, depth_here, base + ".inc", fuse,
-                                 "QG_OUT" if j == 0 else "QG_OUT_ACC", sync, wide_here, lazy_sub, const_factor, min_terms, scaled)
+                                 "QG_OUT" if j == 0 else "QG_OUT_ACC", sync, wide_here, lazy_sub, const_factor, min_terms, scaled, derived=derived)
             write_part(layout, suffix, j, len(parts), base, body, len(part), n_consts, part_slots, slots_in_regs, wgs, fence, threads, sync)
             names.append(base + ".hip")
-        write_kernel_table(layout, suffix, k, code, n_consts, n_tables, ncols, len(parts), scaled)
+        write_kernel_table(layout, suffix, k, code, n_consts, n_tables, ncols, len(parts), scaled, derived)
         names.append("quotient_gen_%s%s.hip" % (layout, suffix))
         written.append((k, suffix, names))
     return written
@@ -382,6 +453,7 @@ def generate(layout, all_variants=False):
 WIDE_MAX_OTHER_PRODUCTS = int(os.environ.get("QG_WIDE_OTHER", "0"))     # other multiplications allowed while a constraint's wide sum is open
 WIDE_ANY_CONST_MUL = os.environ.get("QG_WIDE_ANY_CONST", "1") != "0"   # constraints whose alpha power is not a fused dot term close at their constant too
 SCALED_TABLES = os.environ.get("QG_SCALED_TABLES", "1") != "0"         # multiplier-only tables from a 2^24-fold copy (r280 products)
+DERIVED_COLUMNS = os.environ.get("QG_DERIVED", "1") != "0"             # recipes over one trace column read from a derived column (A/B: QG_DERIVED=0)
 WIDE_MAX_SPAN = int(os.environ.get("QG_WIDE_SPAN", "1000"))            # program instructions from its first product to its alpha multiplication
 # the parts (variant suffix, part number) whose constraints' top-level products accumulate in a second wide accumulator (see
 # plan_wide_constraints); QG_WIDE_PARTS="starknet:1,starknet:3,..." overrides for A/B builds
@@ -390,6 +462,9 @@ WIDE_MAX_SPAN = int(os.environ.get("QG_WIDE_SPAN", "1000"))            # program
 # to get a wide sum of its own).  The instruction counts fall everywhere; the time
 # follows only where the register allocator keeps its spills (a second 38-register accumulator beside the dot product's) - part 4
 # of starknet is faster as it was, with a shallower prefetch.
+# With the decoded flags read from a derived column (rematerialize_cheap_slots: starknet part 0 and the recursive kernel lose nearly
+# half their operand loads) those two were rebuilt at depth 2 / 3 / 4 (profiles/quotient_derived_flag_column.json): starknet part 0
+# 18.78 / 18.82 / 18.94 ms (2 and 3 within the launches' own scatter: 3 stays), recursive 50.13 / 50.75 / 51.03 ms (2 stays).
 PART_TUNING = {"starknet": {("", 0): (True, 3, True, True, 1), ("", 1): (True, 2, True, True, 1), ("", 2): (True, 3, False, False, 1),
                             ("", 3): (True, 3, True, True, 2), ("", 4): (True, 2, False, False, 2), ("", 5): (True, 3, True, True, 1)},
                "recursive": {("", 0): (True, 2, True, True, 1),
@@ -501,8 +576,10 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
 
 
 def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPTH, inc_name, FUSE_ALPHA_DOT_PRODUCTS=False, out_macro="QG_OUT",
-                  sync_every=0, wide_products=False, lazy_sub=False, const_factor=False, min_terms=1, scaled_tables=()):
-    """the straight-line body of one (part) program -> csrc/<inc_name>"""
+                  sync_every=0, wide_products=False, lazy_sub=False, const_factor=False, min_terms=1, scaled_tables=(), derived=()):
+    """the straight-line body of one (part) program -> csrc/<inc_name>.  `derived`: the derived columns SRC_DERIVED operands name
+    (rematerialize_cheap_slots); the body reads them through QG_DERIVED_RAW and carries a fallback definition of that macro over
+    the real column, for a harness that defines only the other operand macros and fills only the real columns."""
     n_instr = len(ins)
     # ---- memory operands in program order: loaded PREFETCH_DEPTH operands ahead into a rotating set of registers
     mem_ops = []                                    # (pc, macro text)
@@ -510,6 +587,9 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
         if op <= OP_MUL and kind == SRC_TRACE:
             assert (w1 >> 24) < ncols
             mem_ops.append((pc, "QG_TRACE_RAW(%d, %du, %%s)" % (w1 >> 24, w1 & 0xffffff)))
+        elif op <= OP_MUL and kind == SRC_DERIVED:
+            assert (w1 >> 24) < len(derived)
+            mem_ops.append((pc, "QG_DERIVED_RAW(%d, %du, %%s)" % (w1 >> 24, w1 & 0xffffff)))
         elif op <= OP_MUL and kind == SRC_TABLE:
             assert w1 < n_tables
             if w1 in scaled_tables:          # its 2^24-fold copy: descriptor n_tables + j of the launch's descriptor array
@@ -549,7 +629,9 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
     body = "\n".join(out)
     regs = "    Fp " + ", ".join("m%d" % k for k in range(D)) + ";\n"
     prime = "".join("    m%d = %s;\n" % (j, mem_ops[j][1] % "i32") for j in range(D))
-    inc = _INC_TEMPLATE % dict(layout=layout, regs=regs, prime=prime, body=body, depth=D,
+    used = sorted(set(w1 >> 24 for op, _, kind, w1 in ins if op <= OP_MUL and kind == SRC_DERIVED))
+    inc = _INC_TEMPLATE % dict(layout=layout, regs=regs, prime=prime, body=body, depth=D, derived_begin=_derived_fallback(derived, used),
+                               derived_end=_DERIVED_FALLBACK_END % "".join("#undef QG_DERIVED_FALLBACK_%d\n" % k for k in used) if used else "",
                                wide=("    QgWide wd;\n" if stats["fused"] else "") + ("    QgWide wq;\n" if stats["wide_terms"] else ""),
                                temp_acc=", acc4 = fl_zero()" if any(d == TEMP_ACC for _, d, _, _ in ins) else "")
     name = inc_name
@@ -566,11 +648,48 @@ _INC_TEMPLATE = '''// GENERATED by tools/gen_quotient.py - DO NOT EDIT.  The bod
 // operand macros of quotient_gen.h (operand loads issued %(depth)d operands ahead).  Included by the quotient_gen_%(layout)s*.hip
 // wrappers (device) and, with host definitions of the same macros, by tests/cpp/quotient_gen_host_test.cpp, which runs it on
 // the CPU against the oracle's constraint VM.
-    Fl acc0 = fl_zero(), acc1 = fl_zero(), acc2 = fl_zero(), acc3 = fl_zero()%(temp_acc)s;
+%(derived_begin)s    Fl acc0 = fl_zero(), acc1 = fl_zero(), acc2 = fl_zero(), acc3 = fl_zero()%(temp_acc)s;
 %(wide)s%(regs)s    uint32_t i32 = (uint32_t)(lane < N ? lane : N - 1);
 %(prime)s    QG_POINT_LOOP_BEGIN
 %(body)s
     QG_POINT_LOOP_END
+%(derived_end)s'''
+
+
+def _small_multiple(expr, k):
+    """k x expr (k >= 1) with fp_dbl / fp_add"""
+    if k == 1:
+        return expr
+    if k % 2 == 0:
+        return "fp_dbl(%s)" % _small_multiple(expr, k // 2)
+    return "fp_add(%s, %s)" % (_small_multiple(expr, k - 1), expr)
+
+
+def _derived_fallback(derived, used):
+    """QG_DERIVED_RAW where nobody defined it: a cell of derived column k computed from the real column, fully reduced (fp252.h)"""
+    if not used:
+        return ""
+    lines = ["// Operands QG_DERIVED_RAW(k, off, idx) are cells of DERIVED COLUMNS (tools/gen_quotient.py derived_column_of): the device builds",
+             "// them once per launch (quotient_derive.h).  Where the includer does not define the macro, the cell is computed here, from the",
+             "// column it derives from - the same fully reduced value.",
+             "#ifndef QG_DERIVED_RAW", "#define QG_DERIVED_FALLBACK", "#define QG_DERIVED_RAW(k, off, idx) QG_DERIVED_FALLBACK_##k(off, idx)", "#endif",
+             "#ifdef QG_DERIVED_FALLBACK"]
+    for k in used:
+        col, terms = derived[k]
+        cell = lambda off: "QG_TRACE_RAW(%d, (off) + %du, idx)" % (col, off)
+        pos = [_small_multiple(cell(off), c) for off, c in terms if c > 0]
+        neg = [_small_multiple(cell(off), -c) for off, c in terms if c < 0]
+        total = lambda xs: xs[0] if len(xs) == 1 else "fp_add(%s, %s)" % (total(xs[:-1]), xs[-1])
+        expr = total(pos) if not neg else "fp_sub(%s, %s)" % (total(pos) if pos else "fp_zero()", total(neg))
+        lines.append("#define QG_DERIVED_FALLBACK_%d(off, idx) %s" % (k, expr))
+    lines.append("#endif")
+    return "\n".join(lines) + "\n"
+
+
+_DERIVED_FALLBACK_END = '''#ifdef QG_DERIVED_FALLBACK
+%s#undef QG_DERIVED_RAW
+#undef QG_DERIVED_FALLBACK
+#endif
 '''
 
 
@@ -646,7 +765,7 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
             elif kind == SRC_CONST:
                 assert w1 < n_consts
                 src = ("QG_CONST_R280(%d)" if op == OP_MUL else "QG_CONST(%d)") % w1
-            elif kind in (SRC_TRACE, SRC_TABLE):
+            elif kind in (SRC_TRACE, SRC_TABLE, SRC_DERIVED):
                 src = "fl_from_fp(m%d)" % (mem_index[pc] % D)
             else:
                 assert kind == SRC_X
@@ -943,7 +1062,7 @@ QGenPart quotient_gen_%(layout)s%(suffix)s_p%(part)d() { return QGenPart{%(wgs)d
         f.write(src)
 
 
-def write_kernel_table(layout, suffix, variant, code, n_consts, n_tables, ncols, n_parts, scaled=()):
+def write_kernel_table(layout, suffix, variant, code, n_consts, n_tables, ncols, n_parts, scaled=(), derived=()):
     """the host-side entry of one variant: what ss_eval_quotient looks up by the program's hash"""
     decl = "".join("QGenPart quotient_gen_%s%s_p%d();\n" % (layout, suffix, j) for j in range(n_parts))
     parts = ", ".join("quotient_gen_%s%s_p%d()" % (layout, suffix, j) for j in range(n_parts))
@@ -960,14 +1079,18 @@ namespace ss {
 const QGenKernel &quotient_gen_%(layout)s%(suffix)s() {
     // tables the kernels read from a copy times 2^24 (multiplier-only tables: tools/gen_quotient.py generate): descriptor n_tables + j
     static const uint32_t scaled[] = {%(scaled)s};
+    // derived columns the kernels read (tools/gen_quotient.py derived_column_of; built per launch, quotient_derive.h): the trace column,
+    // then (row offset, coefficient) per term
     static const QGenKernel k = {"%(layout)s", 0x%(hash)016xull, %(n_instr)du, %(n_consts)du, %(n_tables)du, %(ncols)du, %(variant)du, %(n_parts)du, {%(parts)s},
-                                 %(n_scaled)du, scaled};
+                                 %(n_scaled)du, scaled, %(n_derived)du, {%(derived)s}};
     return k;
 }
 
 }  // namespace ss
 """ % dict(layout=layout, suffix=suffix, variant=variant, n_parts=n_parts, hash=code_hash(code), n_instr=len(code) // 2, n_consts=n_consts,
-           n_tables=n_tables, ncols=ncols, decl=decl, parts=parts, n_scaled=len(scaled), scaled=", ".join("%du" % t for t in scaled) if scaled else "0u")
+           n_tables=n_tables, ncols=ncols, decl=decl, parts=parts, n_scaled=len(scaled), scaled=", ".join("%du" % t for t in scaled) if scaled else "0u", n_derived=len(derived),
+           derived=", ".join("{%du, %du, {%s}, {%s}}" % (col, len(terms), ", ".join("%du" % off for off, _ in terms), ", ".join("%d" % c for _, c in terms))
+                             for col, terms in derived))
     with open(os.path.join(OUT_DIR, "quotient_gen_%s%s.hip" % (layout, suffix)), "w") as f:
         f.write(src)
     if not suffix:                                  # the same list for the host build of the bodies (tests/cpp/quotient_gen_host_test.cpp)
