@@ -695,6 +695,104 @@ int ssh_prove_files_device(ss_ctx *ctx, int layout, const uint8_t *trace_bin, ui
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }
 
+}  // extern "C"
+namespace {
+// the claim, the options and the coin's seed as the entry points take them (options: as ssh_prove; NULL = the defaults)
+struct ClaimArgs { Claim claim; ProofOptions opt; Digest seed; };
+ClaimArgs unpack_claim(ssh_air *air_h, int tree_kind, uint32_t n_friendly_layers, int coin_kind, const uint8_t seed[32], const uint32_t options[5]) {
+    ClaimArgs a;
+    a.claim.air = reinterpret_cast<Air *>(air_h); a.claim.tree_kind = tree_kind; a.claim.n_friendly_layers = n_friendly_layers; a.claim.coin_kind = coin_kind;
+    if (options) {
+        a.opt.num_queries = options[0]; a.opt.lde_blowup_factor = options[1]; a.opt.grinding_factor = options[2];
+        a.opt.fri_folding_factor = options[3]; a.opt.fri_max_remainder_coeffs = options[4];
+    }
+    memcpy(a.seed.data(), seed, 32);
+    return a;
+}
+}  // namespace
+extern "C" {
+
+// files -> proof over the ranks of a group (ssh_prove_files_device's timer - cli/src/main.rs:200-202: generate_trace + prove - around
+// ssh_prove_sharded_blocks' distribution).  Every rank calls it with its own context and AIR handle, the same files and the same claim;
+// group / rccl: as ssh_prove_sharded.  Every rank makes the WHOLE base trace in HBM from the 25 MB of the files (the generation costs
+// what one transform costs; replicating it needs no exchange), so the input's refusals - the host checks and the kernels' status bits -
+// come out the same on every rank BEFORE the first collective is entered: no rank waits for one whose files were refused.  A rank then
+// keeps the columns with c % world == rank and its rows [rank n / world, (rank + 1) n / world) of the auxiliary columns (npc, memory,
+// range check; for the recursive layout the diluted pair too) as blocks of their own, and frees every column it does not own before
+// the first transform; the extension trace is built from the blocks (build_extension_blocks, checked) inside the call.  pow_nonce:
+// NULL = grind, else the nonce to use (ShardedProver::set_pow_nonce).  times_out (optional, 2 doubles): until this rank's columns were
+// final and checked, and the whole call.  The proof (reference wire format) comes out on rank 0 (*proof_len = 0 on the others) and is
+// the one ssh_prove_files_device writes for the same statement.
+int ssh_prove_files_sharded_device(ss_ctx *ctx, int layout, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len,
+                                   uint32_t rc_min, uint32_t rc_max, uint64_t n_steps, const uint32_t *segments, const uint32_t *mem_addresses,
+                                   const uint64_t *mem_values, uint64_t n_mem, const uint64_t *const *instances, const uint64_t *counts, ssh_air *air_h,
+                                   int tree_kind, uint32_t n_friendly_layers, int coin_kind, const uint8_t seed[32], const uint32_t options[5], uint32_t rank,
+                                   uint32_t world, ssh_local_group *group, ssh_rccl_group *rccl, const uint64_t *pow_nonce, double *times_out,
+                                   uint8_t **proof_bytes, uint64_t *proof_len) {
+    std::shared_ptr<LocalGroup> *lg = reinterpret_cast<std::shared_ptr<LocalGroup> *>(group);
+    try {
+        if (proof_bytes && proof_len) { *proof_bytes = nullptr; *proof_len = 0; }
+        if (!ctx || !air_h || !seed || (!group && !rccl)) throw std::runtime_error("ssh_prove_files_sharded_device: NULL argument");
+        const auto t_start = std::chrono::steady_clock::now();
+        if (rank >= world) throw std::runtime_error("ssh_prove_files_sharded_device: rank " + std::to_string(rank) + " of " + std::to_string(world));
+        std::unique_ptr<Transport> local = lg ? make_local_transport(*lg, rank) : nullptr;
+        Transport *comm = lg ? local.get() : reinterpret_cast<Transport *>(rccl);
+        if (comm->world != world || comm->rank != rank) throw std::runtime_error("ssh_prove_files_sharded_device: the group has another number of ranks, or this is another rank of it");
+        const TraceJob job = make_trace_job(layout, trace_bin, trace_len, memory_bin, memory_len, rc_min, rc_max, n_steps, segments, mem_addresses, mem_values,
+                                            n_mem, instances, counts);
+        const ClaimArgs ca = unpack_claim(air_h, tree_kind, n_friendly_layers, coin_kind, seed, options);
+        if (ca.claim.air->num_base_columns != job.ncols) throw std::runtime_error("ssh_prove_files_sharded_device: the AIR is another layout's");
+        if (job.n % world) throw std::runtime_error("ssh_prove_files_sharded_device: the trace's rows do not divide over the ranks");
+        // everything below lives in the context's pool and goes back to it on every way out (the buffers are RAII), after what this
+        // rank enqueued has ended (the guard is declared last, so it goes first)
+        const std::vector<uint32_t> aux_cols = layout == 1 ? std::vector<uint32_t>{3, 4, 5, 1, 2} : std::vector<uint32_t>{5, 6, 7};   // in TraceColumns' order
+        std::vector<std::unique_ptr<DeviceBuffer>> cols(job.ncols), aux(aux_cols.size());
+        Matrix ext;                                      // the extension trace's row blocks: alive until the proof is out
+        struct SyncOnExit { ss_ctx *ctx; ~SyncOnExit() { (void)ss_ctx_sync(ctx); } } sync_on_exit{ctx};
+        std::vector<uint64_t *> d_cols(job.ncols);
+        for (uint32_t c = 0; c < job.ncols; ++c) { cols[c].reset(new DeviceBuffer(ctx, 32 * (size_t)job.n)); d_cols[c] = cols[c]->u64(); }
+        job.run_device(ctx, d_cols.data());             // returns with the columns final, or throws the input's refusal: no collective yet
+        const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+        const uint64_t block_rows = job.n / world;       // this rank's rows of the auxiliary columns
+        for (size_t k = 0; k < aux_cols.size(); ++k) {
+            aux[k].reset(new DeviceBuffer(ctx, 32 * (size_t)block_rows));
+            if (ss_dev_copy(ctx, aux[k]->u64(), d_cols[aux_cols[k]] + 4 * (size_t)rank * block_rows, 32 * (size_t)block_rows) != SS_OK) throw std::runtime_error(ss_last_error());
+        }
+        std::map<uint32_t, uint64_t *> mine;
+        for (uint32_t c = 0; c < job.ncols; ++c) {
+            if (c % world == rank) mine[c] = d_cols[c];
+            else cols[c].reset();                        // (the pool is ordered by the context's stream: the copies above come first)
+        }
+        TraceColumns tc;
+        tc.npc = aux[0]->u64(); tc.memory = aux[1]->u64(); tc.range_check = aux[2]->u64(); tc.trace_len = job.n;
+        if (layout == 1) { tc.diluted_unordered = aux[3]->u64(); tc.diluted_ordered = aux[4]->u64(); }
+        BlockGather gather;
+        gather.rank = rank; gather.world = world;
+        gather.all_gather = [&](const std::vector<uint8_t> &bytes) { return comm->all_gather(ctx, bytes); };
+        ShardedProver prover(ctx, ca.claim, *comm, ca.opt);
+        if (pow_nonce) prover.set_pow_nonce(*pow_nonce);
+        prover.set_extension_blocks([&](const std::vector<Felt> &ch) {
+            ext = build_extension_blocks(ctx, layout == 1 ? "recursive" : "starknet", tc, ch, gather, true);
+            return ext.cols;
+        });
+        Proof proof;
+        const bool have = prover.prove(ca.seed, mine, nullptr, job.n, &proof);
+        if (ss_ctx_sync(ctx) != SS_OK) throw std::runtime_error(ss_last_error());
+        if (times_out) { times_out[0] = gen_s; times_out[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
+        if (have && proof_bytes && proof_len) {
+            const std::vector<uint8_t> b = proof.serialize_wire();
+            *proof_bytes = (uint8_t *)malloc(b.size());
+            memcpy(*proof_bytes, b.data(), b.size());
+            *proof_len = b.size();
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        if (lg) local_group_fail(**lg);
+        return 1;
+    }
+}
+
 // ---- the 64-bit field's claim (goldilocks_prover.hpp; cli/src/main.rs:103-133).  options: {num_queries, log_blowup, grinding, fold,
 // max_remainder, sha256 (0 / 1)}.  mask: nmask x (column, offset).  ext_cb fills `num_ext` device pointers (the extension trace's
 // coordinate columns) for the challenges (3 u64 each); prog_cb returns the lowered composition program for challenges and alpha as a

@@ -774,7 +774,7 @@ TRACE_STATS_KEYS = ("bytes_uploaded", "pedersen_on_host", "pedersen_on_device", 
 
 
 def trace_last_stats():
-    """what the last device generation on this thread (device_base_trace, prove_files_device) moved (host_capi.cpp ssh_trace_last_stats_n)
+    """what the last device generation on this thread (device_base_trace, prove_files_device, prove_files_sharded_device) moved (host_capi.cpp ssh_trace_last_stats_n)
     -> {"bytes_uploaded", "pedersen_on_host", "pedersen_on_device", "templates_uploaded"}: the generator's uploads in bytes, the given
     Pedersen instances whose curve steps ran on the host / on the device, the builtin templates uploaded (all builtins); and
     {"bitwise_on_host", "bitwise_on_device", "poseidon_on_host", "poseidon_on_device", "ec_op_on_host", "ec_op_on_device"}: the given
@@ -1026,6 +1026,35 @@ def prove_sharded(ctx, air: HostAir, tree_kind, n_friendly, coin_kind, seed, ran
     raw = bytes(bytearray(out[:n.value]))
     load().ssh_free(out)
     return raw
+
+
+def prove_files_sharded_device(ctx, layout, trace_bin: bytes, memory_bin: bytes, pi, private_input, air: HostAir, tree_kind, n_friendly, coin_kind, seed,
+                               rank, world, group, options=None, pow_nonce=None):
+    """`sandstorm-cli prove` in one call over `world` ranks (host_capi.cpp ssh_prove_files_sharded_device): every rank calls it with its own
+    context and AIR handle and the same files; each makes the whole base trace on its device from the files' bytes (the input's
+    refusals are raised on every rank before any rank enters a collective), keeps its own columns and its rows of the auxiliary
+    columns, builds its blocks of the extension trace and proves with the others as prove_sharded does.  group: a LocalGroup, this
+    rank's RcclGroup or a CallbackGroup.  pow_nonce: use this proof-of-work nonce instead of grinding.
+    -> (proof bytes in the reference's wire format on rank 0 / None on the others, {"trace_gen_s", "total_s"})"""
+    options = options or ProofOptions()
+    args, keep_args = _trace_job_args(layout, trace_bin, memory_bin, pi, private_input)
+    opts = (C.c_uint32 * 5)(options.num_queries, options.lde_blowup_factor, options.grinding_factor,
+                            options.fri_folding_factor, options.fri_max_remainder_coeffs)
+    fn = load().ssh_prove_files_sharded_device
+    fn.argtypes = [C.c_void_p] + _TRACE_JOB_ARGTYPES + [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                                        C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+    out, ln, times = C.POINTER(C.c_uint8)(), C.c_uint64(), (C.c_double * 2)()
+    local = isinstance(group, LocalGroup)
+    nonce = None if pow_nonce is None else C.byref(C.c_uint64(int(pow_nonce)))
+    _check(fn(ctx.handle, *args, air.h, tree_kind, n_friendly, coin_kind, None if seed is None else bytes(seed), opts, rank, world,
+              group.h if local else None, None if local else group.h, nonce, times, C.byref(out), C.byref(ln)))
+    del keep_args
+    raw = None
+    if ln.value:
+        raw = bytes(bytearray(out[:ln.value]))
+        load().ssh_free(out)
+    return raw, {"trace_gen_s": times[0], "total_s": times[1]}
 
 
 class HostCoin:
