@@ -2590,7 +2590,14 @@ static ss_status eval_quotient_impl(ss_ctx *ctx, const ss_air_program *prog, con
         bool variant_missing = false;
         const QGenKernel *gen = quotient_gen_find(prog->code, prog->n_instr, &variant_missing);
         if (!gen && variant_missing) return fail(SS_ERR_UNSUPPORTED, "SS_QG_VARIANT names a kernel variant this build does not hold (make QG_AB=1)");
-        if (gen && gen->n_consts == prog->n_consts && gen->n_tables == prog->n_tables && gen->ncols <= ncols)
+        // the kernels hold some constants as code (QGenKernel::baked: small structural multiples); the hash covers the code words only,
+        // so a program with the same code and another value there is not theirs - it is interpreted, like any unknown program
+        bool baked_ok = gen != nullptr && gen->n_consts == prog->n_consts;
+        for (uint32_t j = 0; baked_ok && j < gen->n_baked; ++j) {
+            const QGenBaked &b = gen->baked[j];
+            baked_ok = b.index < prog->n_consts && memcmp(prog->consts + 4 * (size_t)b.index, b.value, sizeof(b.value)) == 0;
+        }
+        if (gen && baked_ok && gen->n_consts == prog->n_consts && gen->n_tables == prog->n_tables && gen->ncols <= ncols)
             return eval_quotient_compiled(ctx, *gen, prog, d_lde_cols, ncols, log_N, log_blowup, offset, d_out, row0, N, block ? block_rows : 0);
     }
     return eval_quotient_interpreted(ctx, prog, d_lde_cols, ncols, log_N, log_blowup, offset, row0, N, block, d_out);

@@ -159,6 +159,32 @@ SS_HD Fl fl_sub_c(const Fl &a, const Fl &b) {
 }
 SS_HD Fl fl_sub8p(const Fl &a, const Fl &b) { return fl_sub_c<8, 2>(a, b); }
 
+// C * a for a small integer C (2 .. 8), limb-wise: a shift where C is a power of two, else shifts and adds along C's binary
+// expansion (6 l = ((l << 1) + l) << 1: a shift-and-add and a shift) - never a 32-bit multiply, which issues at quarter rate.
+// No carries, no 64-bit operations, no VCC: 9 to 27 vector instructions against the 185 of a product by the constant C.
+//   input : value < V p, limbs < L              (any lazy value with C L <= 2^32)
+//   output: value < C V p, limbs < C L          (bounds multiply, as fl_add's add: exactly the value C a, not reduced)
+// The constraint kernels (tools/gen_quotient.py) count a value's bound b in units of a normalised value or one fl_sub_c<2, 1> result
+// (value < 2 b p; limbs <= b x (2^28 + 2, 2^28 - 1 x 5, 2^28 - 1 + 2^25, 2^28 + 1, 2^28 - 1)), keep C b <= 8 (value < 16 p < 2^256,
+// limbs < 2^32) and take the negative multiple as fl_sub_c<C', F>(fl_zero(), fl_scale<C>(a)) with the template whose limb-wise
+// constant covers C b such units:  C b = 2: <8, 2>, result <= 8 p, bound 4;  3 or 4: <16, 4>, result <= 16 p, bound 8;  above: a weak
+// reduction first, then <2, 1> (tests/test_fl_scale_host.py runs every pair at the top of these limb bounds).
+template <u32 C>
+SS_HD u32 fl_scale_limb(u32 l) {
+    static_assert(C >= 1 && C <= 8, "fl_scale: multiples 2 .. 8 (larger ones are composed, with weak reductions between)");
+    if constexpr (C == 1) return l;
+    else if constexpr ((C & (C - 1)) == 0) return l << (C == 2 ? 1 : C == 4 ? 2 : 3);
+    else if constexpr (C % 2 == 0) return fl_scale_limb<C / 2>(l) << 1;
+    else return fl_scale_limb<C - 1>(l) + l;
+}
+template <u32 C>
+SS_HD Fl fl_scale(const Fl &a) {
+    Fl r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.l[i] = fl_scale_limb<C>(a.l[i]);
+    return r;
+}
+
 // A value the optimiser cannot see through: keeps `m * 2^24` a v_mad_u64_u32 that
 // accumulates in place instead of a 64-bit shift + 64-bit add pair.
 SS_HD u32 fl_opaque(u32 x) {

@@ -48,6 +48,10 @@ struct QGenPart {
     uint32_t n_instr;                            // program instructions in this part
     hipError_t (*launch)(hipStream_t, const QGenArgs &, uint32_t blocks);
 };
+struct QGenBaked {
+    uint32_t index;                              // a constant some part multiplies by as shifts and adds (QG_SCALE below) ...
+    uint64_t value[4];                           // ... and the interchange image the program's constant table must hold for it
+};
 struct QGenKernel {
     const char *layout;
     uint64_t code_hash;                          // FNV-1a of the (whole) program's code words
@@ -55,6 +59,8 @@ struct QGenKernel {
     uint32_t variant;                            // tools/gen_quotient.py VARIANTS; ss_eval_quotient takes 0 (SS_QG_VARIANT overrides)
     uint32_t n_parts;
     QGenPart parts[QG_MAX_PARTS];
+    uint32_t n_baked;                            // constants held as code: a program whose table differs in one of them is interpreted
+    const QGenBaked *baked;
     uint32_t n_scaled;                           // tables the kernels read from a 2^24-fold copy (multiplier-only tables): their numbers;
     const uint32_t *scaled;                      // copy j is addressed by descriptor n_tables + j
     uint32_t n_derived;                          // derived columns the kernels read through QG_DERIVED_RAW (quotient_derive.h)
@@ -144,6 +150,11 @@ __device__ __forceinline__ void qg_wide_tail(QgWide &w, const Fl &l) {
 #define QG_CONST_R280(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k) + 9)
 #define QG_CONST_R280_UP(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k) + 18)
 #define QG_CONST_R280_UPN(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k) + 27)
+// multiples by a structural small integer (tools/gen_quotient.py structural_constants, scale_plan): constant k is +-(f f' ...), checked
+// against the program's constant table before the launch (QGenKernel::baked) - shifts and adds instead of a product by QG_CONST_R280(k)
+#define QG_SCALE(k, f, x) fl_scale<f>(x)
+#define QG_RESCALE(f, x) fl_scale<f>(x)
+#define QG_NEGSCALED(C, F, x) fl_sub_c<C, F>(fl_zero(), x)
 // keep a load where the generator put it: ALU instructions and LDS writes may still be scheduled across, vector-memory
 // instructions and LDS reads may not (an LDS read of a constant depends on nothing: unpinned, hundreds of them float
 // to the top of the point and sit in registers until used)

@@ -65,12 +65,89 @@ def template_program(layout):
         n = 1 << 18
     code, consts, n_slots, specs = air.dump(n, ch, alpha)
     ncols = air.num_base_columns + air.num_extension_columns
+    # the same program with other challenges, another composition coefficient and (starknet) another statement: what a constant is
+    # in BOTH dumps it is by the layout's structure, not by the proof (structural_constants)
+    ch2 = [oracle.to_mont([pow(11, 5 + 7 * i, P)])[0] for i in range(6)]
+    alpha2 = oracle.to_mont([pow(3, 101, P)])[0]
+    air2 = air
+    if layout == "starknet":
+        _, _, pi2 = starknet_example(12)
+        air2 = hostlib.StarknetHostAir(None, pi2, 21)
+    code2, consts2, _, _ = air2.dump(n, ch2, alpha2)
+    if air2 is not air:
+        air2.close()
     air.close()
+    assert np.array_equal(np.asarray(code, dtype=np.uint32), np.asarray(code2, dtype=np.uint32)), "the program depends on the statement"
     template_program.specs[layout] = specs
+    template_program.structural[layout] = structural_constants(decode(np.asarray(code, dtype=np.uint32)), consts, consts2)
     return np.asarray(code, dtype=np.uint32), len(consts), n_slots, len(specs), ncols
 
 
 template_program.specs = {}                         # layout -> the table specs of its last template (generate reads the tables' kinds)
+template_program.structural = {}                    # layout -> its structural small constants (structural_constants)
+FIELD_P = 2**251 + 17 * 2**192 + 1
+SMALL_MULTIPLE_MAX = 256                            # |c| up to which a structural constant is a candidate for shifts and adds
+
+
+def felt_of(words):
+    """4 x u64 little endian -> integer"""
+    return sum(int(w) << (64 * k) for k, w in enumerate(words))
+
+
+def structural_constants(ins, consts, consts2):
+    """The compiled kernel is chosen by the hash of the code words; the constant table arrives at run time.  A constant may be baked
+    into the code (a multiplication by it written as shifts and adds) only if it is the layout's, not the proof's: the SAME value in
+    two dumps that differ in challenges, composition coefficient and statement, a small integer c (2 <= |c| <= SMALL_MULTIPLE_MAX), and
+    a multiplier somewhere ("MUL acc, c" or "MOV acc, c; MUL acc, x": a boundary value that happens to be small is subtracted, not
+    multiplied by).  -> {constant index: (c, Montgomery image as an integer)}.  The launch still compares every baked constant with
+    the table it is given (QGenKernel::baked) and interprets the program on a mismatch: a wrong guess here costs time, not the result."""
+    consts, consts2 = [felt_of(c) for c in consts], [felt_of(c) for c in consts2]
+    rinv = pow(1 << 256, -1, FIELD_P)
+    mul_use = set()
+    for pc, (op, d, kind, w1) in enumerate(ins):
+        if op <= OP_MUL and kind == SRC_CONST:
+            nxt = ins[pc + 1] if pc + 1 < len(ins) else None
+            if op == OP_MUL or (op == OP_MOV and nxt is not None and nxt[0] == OP_MUL and nxt[1] == d and not (nxt[2] == SRC_ACC and (nxt[3] & 3) == d)):
+                mul_use.add(w1)
+    out = {}
+    for k in sorted(mul_use):
+        if consts[k] != consts2[k] or consts[k] >= FIELD_P:
+            continue
+        v = consts[k] * rinv % FIELD_P
+        c = v if v <= SMALL_MULTIPLE_MAX else v - FIELD_P if FIELD_P - v <= SMALL_MULTIPLE_MAX else None
+        if c is not None and abs(c) >= 2:
+            out[k] = (c, consts[k])
+    return out
+
+
+PRODUCT_COST = 185      # vector instructions of fl_mul_r280 (profiles/r04_quotient_algebra.txt)
+WIDE_TERM_COST = 162    # a term of a wide sum: 81 multiply-adds at half rate
+REDUCE_COST = 54        # fl_weak_reduce
+
+
+def scale_plan(c, b):
+    """|c| x (a lazy value of bound b) by fl_scale<f> steps with f x bound <= MAX_BOUND, a weak reduction wherever the next factor
+    would pass it: c's factors <= MAX_BOUND, largest first (10 = 5 x 2, 16 = 8 x 2, 256 = 8 x 8 x 4; 11 has no such plan).
+    -> (steps: "R" or a factor, cost in vector instructions, bound of the result) or None"""
+    c = abs(c)
+    factors = []
+    while c > 1:
+        f = next((f for f in range(min(c, MAX_BOUND), 1, -1) if c % f == 0), None)
+        if f is None:
+            return None
+        factors.append(f)
+        c //= f
+    steps, cost = [], 0
+    for f in factors:
+        if b * f > MAX_BOUND:
+            steps.append("R")
+            cost += REDUCE_COST
+            b = 1
+        steps.append(f)
+        b *= f
+        # a limb of f x: one shift (power of two), else a shift-and-add per further set bit and a shift per trailing zero
+        cost += 9 * (1 if f & (f - 1) == 0 else bin(f).count("1") - 1 + (1 if f % 2 == 0 else 0))
+    return steps, cost, b
 
 
 def decode(code):
@@ -411,7 +488,7 @@ def generate(layout, all_variants=False):
             # (VERDICT r4 #4).  What is copied is periodic: at most 2^17 entries per table, a few megabytes per launch in all.
             full_length = {t for t, spec in enumerate(template_program.specs[layout]) if spec[0] == "inverse"}
             scaled = sorted(t for t, ops in uses.items() if ops == {OP_MUL} and t not in full_length)
-        names = []
+        names, baked = [], set()
         # the parts that rematerialise (the decoded flags: recomputed at their uses instead of parked, 17 -> 6 slots) - and what of
         # that is a row of a derived column, read instead of recomputed (one list per layout: the launch builds the columns once)
         compacted = [compact_slots(part) for part in parts]
@@ -432,7 +509,9 @@ def generate(layout, all_variants=False):
                 lds = part_slots * 2 * threads * 16 + n_consts * 36 * 4
                 assert lds * wgs <= LDS_BYTES_PER_CU, "%s%s part %d: %d slots + constants = %d B of LDS x %d workgroups per CU" % (layout, suffix, j, part_slots, lds, wgs)
             base = "quotient_gen_%s%s_p%d" % (layout, suffix, j)
-            wide_here, depth_here, lazy_sub, const_factor, min_terms = PART_TUNING.get(layout, {}).get((suffix, j), (False, depth, False, False, 1))
+            wide_here, depth_here, lazy_sub, const_factor, min_terms, small_here, dedup_here = PART_TUNING.get(layout, {}).get((suffix, j), (False, depth, False, False, 1, False, False))
+            small_here = os.environ["QG_SMALL_MULTIPLES"] != "0" if "QG_SMALL_MULTIPLES" in os.environ else small_here      # A/B builds: every part alike
+            dedup_here = os.environ["QG_DEDUP"] != "0" if "QG_DEDUP" in os.environ else dedup_here
             min_terms = int(os.environ.get("QG_WIDE_MIN_TERMS", min_terms))
             if "QG_WIDE_PARTS" in os.environ:                 # A/B builds (tools/qg_wide_ab.sh): the same choice for every part
                 wide_here = ("%s:%d" % (layout, j)) in os.environ["QG_WIDE_PARTS"].split(",") or os.environ["QG_WIDE_PARTS"] == "all"
@@ -440,10 +519,13 @@ def generate(layout, all_variants=False):
             lazy_sub = os.environ["QG_SUB_LAZY2"] != "0" if "QG_SUB_LAZY2" in os.environ else lazy_sub
             const_factor = os.environ["QG_CONST_FACTOR"] != "0" if "QG_CONST_FACTOR" in os.environ else const_factor
             body = generate_body(layout, part, n_consts, part_slots, n_tables, ncols, depth_here, base + ".inc", fuse,
-                                 "QG_OUT" if j == 0 else "QG_OUT_ACC", sync, wide_here, lazy_sub, const_factor, min_terms, scaled, derived=derived)
+                                 "QG_OUT" if j == 0 else "QG_OUT_ACC", sync, wide_here, lazy_sub, const_factor, min_terms, scaled, derived=derived,
+                                 small=template_program.structural[layout] if small_here else {}, dedup=dedup_here)
+            baked.update(body["baked"])
             write_part(layout, suffix, j, len(parts), base, body, len(part), n_consts, part_slots, slots_in_regs, wgs, fence, threads, sync)
             names.append(base + ".hip")
-        write_kernel_table(layout, suffix, k, code, n_consts, n_tables, ncols, len(parts), scaled, derived)
+        write_kernel_table(layout, suffix, k, code, n_consts, n_tables, ncols, len(parts), scaled, derived,
+                           [(c, template_program.structural[layout][c][1]) for c in sorted(baked)])
         names.append("quotient_gen_%s%s.hip" % (layout, suffix))
         written.append((k, suffix, names))
     return written
@@ -465,11 +547,20 @@ WIDE_MAX_SPAN = int(os.environ.get("QG_WIDE_SPAN", "1000"))            # program
 # With the decoded flags read from a derived column (rematerialize_cheap_slots: starknet part 0 and the recursive kernel lose nearly
 # half their operand loads) those two were rebuilt at depth 2 / 3 / 4 (profiles/quotient_derived_flag_column.json): starknet part 0
 # 18.78 / 18.82 / 18.94 ms (2 and 3 within the launches' own scatter: 3 stays), recursive 50.13 / 50.75 / 51.03 ms (2 stays).
-PART_TUNING = {"starknet": {("", 0): (True, 3, True, True, 1), ("", 1): (True, 2, True, True, 1), ("", 2): (True, 3, False, False, 1),
-                            ("", 3): (True, 3, True, True, 2), ("", 4): (True, 2, False, False, 2), ("", 5): (True, 3, True, True, 1)},
-               "recursive": {("", 0): (True, 2, True, True, 1),
-                             ("_v2", 0): (True, 2, True, True, 1), ("_v2", 1): (True, 2, True, True, 1),
-                             ("_v3", 0): (True, 2, True, True, 1), ("_v3", 1): (True, 2, True, True, 1), ("_v3", 2): (True, 2, True, True, 1)}}
+# Two further switches per part (profiles/quotient_small_multiples.json): SMALL MULTIPLES - a multiplication by a structural small
+# integer (structural_constants: 2, 4, 6, 8, 10, 16, -2, -4 in the Poseidon rounds, the bit unpackings, the bitwise builtin) as
+# fl_scale shifts and adds where scale_plan prices it below the product - and REPEATED OPERANDS - two consecutive memory operands
+# that name the same cell ("x + x" lowers to MOV acc, T; ADD acc, T) as one load.
+# A part whose scratch (spill) bytes grow under a cut keeps that cut off - the condition the cuts were taken under, checked on the
+# cross-compiled kernels: part 1 spills 76 -> 104 bytes per lane with its two small multiples (off), part 3 0 -> 272 with its 21
+# repeated operands as single loads (off: the shared register lives across the fence between its two uses).
+PART_TUNING = {"starknet": {("", 0): (True, 3, True, True, 1, True, True), ("", 1): (True, 2, True, True, 1, False, True),
+                            ("", 2): (True, 3, False, False, 1, True, True), ("", 3): (True, 3, True, True, 2, True, False),
+                            ("", 4): (True, 2, False, False, 2, True, True), ("", 5): (True, 3, True, True, 1, True, True)},
+               "recursive": {("", 0): (True, 2, True, True, 1, True, True),
+                             ("_v2", 0): (True, 2, True, True, 1, False, False), ("_v2", 1): (True, 2, True, True, 1, False, False),
+                             ("_v3", 0): (True, 2, True, True, 1, False, False), ("_v3", 1): (True, 2, True, True, 1, False, False),
+                             ("_v3", 2): (True, 2, True, True, 1, False, False)}}
 
 
 class WideViolation(Exception):
@@ -479,7 +570,7 @@ class WideViolation(Exception):
         self.k = k
 
 
-def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, scaled_tables=frozenset()):
+def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, scaled_tables=frozenset(), small=frozenset()):
     """Round 4.  A constraint C = sum_i s_i A_i B_i + L (A_i, B_i, L: sums of cells, constants and earlier values;
     most of the program's products sit at this top level) paid a whole Montgomery product per A_i B_i - 81 multiply-adds plus a
     142-instruction reduction - and, where a product waited for its siblings in a scratch slot, a weak reduction, a store and a
@@ -492,8 +583,12 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
     This function finds, in the value graph of the instruction stream, for every fused "MUL acc, alpha^k" (pc in `fused`) the
     flattened signed sum below the multiplied value and its product terms.  -> (wide_mul: pc of a product -> (constraint, sign),
     close: pc of the alpha multiplication -> (g, number of products), struct: pc of an ADD / SUB / RSUB inside the sum ->
-    constraint).  A constraint is named by the pc of its alpha multiplication."""
+    constraint).  A constraint is named by the pc of its alpha multiplication.
+
+    `small`: the constants whose multiples are shifts and adds (structural_constants).  "MOV acc, c; MUL acc, x" with such a c is no
+    product term: c x is a plain value, and where it stands in a constraint's sum it joins the linear part L."""
     nodes = []                                     # (kind, a, b)
+    small_node, small_mul = set(), set()           # CONST nodes of `small`; pcs of the multiplications by them
 
     def new(kind, a=None, b=None):
         nodes.append((kind, a, b))
@@ -505,6 +600,8 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
         src = None
         if op <= OP_MUL:
             src = acc[w1 & 7] if kind == SRC_ACC else slot[w1] if kind == SRC_SLOT else new("CONST" if kind == SRC_CONST else "LEAF")
+            if kind == SRC_CONST and w1 in small:
+                small_node.add(src)
         if op == OP_MOV:
             acc[d] = src
         elif op in (OP_ADD, OP_SUB):
@@ -516,6 +613,8 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
         elif op == OP_MUL:
             if pc in fused or (WIDE_ANY_CONST_MUL and kind == SRC_CONST):      # any scaling by a constant can take the 2^24 back
                 root_of[pc] = acc[d]
+            if src in small_node or acc[d] in small_node:
+                small_mul.add(pc)
             acc[d] = new("MUL", acc[d], src)
             made_at[acc[d]] = pc
             if kind == SRC_TABLE and w1 in scaled_tables:                       # (the table's copy carries 2^24: a plain r280 product)
@@ -551,7 +650,8 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
                 terms.append((sgn, v))
         prods = [(sgn, v) for sgn, v in terms
                  if nodes[v][0] == "MUL" and uses.get(v, 0) == 1 and nodes[v][1] != nodes[v][2] and v not in taken and v not in by_scaled_table
-                 and nodes[nodes[v][2]][0] != "CONST" and (const_factor or nodes[nodes[v][1]][0] != "CONST") and made_at[v] not in root_of]
+                 and nodes[nodes[v][2]][0] != "CONST" and (const_factor or nodes[nodes[v][1]][0] != "CONST") and made_at[v] not in root_of
+                 and nodes[v][1] not in small_node]
         # (a constant that was MOVed into the accumulator and multiplied by a cell is a factor like any other: its R256 limbs are the
         # value c 2^256, so c x cell comes out at the same 2^-24 as the products of two cells - sums of 2^(16 j) x cell_j, fourteen terms
         # long in the range-check and bit-unpacking constraints, become fourteen 81-multiply-add terms and ONE reduction)
@@ -562,7 +662,7 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
         # recursive kernel ran 14 % SLOWER with every constraint widened) - so only constraints whose products follow each other
         first = min(made_at[v] for _, v in prods)
         mine = set(made_at[v] for _, v in prods)
-        between = [pc for pc in range(first, k) if ins[pc][0] in (OP_MUL, OP_INV) and pc not in mine]
+        between = [pc for pc in range(first, k) if ins[pc][0] in (OP_MUL, OP_INV) and pc not in mine and pc not in small_mul]     # (shifts and adds: no columns)
         if len(between) > WIDE_MAX_OTHER_PRODUCTS or k - first > WIDE_MAX_SPAN:
             continue
         g = 1 if sum(1 for sgn, _ in prods if sgn > 0) * 2 >= len(prods) else -1
@@ -576,10 +676,13 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
 
 
 def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPTH, inc_name, FUSE_ALPHA_DOT_PRODUCTS=False, out_macro="QG_OUT",
-                  sync_every=0, wide_products=False, lazy_sub=False, const_factor=False, min_terms=1, scaled_tables=(), derived=()):
+                  sync_every=0, wide_products=False, lazy_sub=False, const_factor=False, min_terms=1, scaled_tables=(), derived=(), small=None, dedup=False):
     """the straight-line body of one (part) program -> csrc/<inc_name>.  `derived`: the derived columns SRC_DERIVED operands name
     (rematerialize_cheap_slots); the body reads them through QG_DERIVED_RAW and carries a fallback definition of that macro over
-    the real column, for a harness that defines only the other operand macros and fills only the real columns."""
+    the real column, for a harness that defines only the other operand macros and fills only the real columns.
+    `small`: the structural small constants whose multiples may be written as shifts and adds (structural_constants; {} = none).
+    `dedup`: two consecutive memory operands that name the same cell are one load."""
+    small = small or {}
     n_instr = len(ins)
     # ---- memory operands in program order: loaded PREFETCH_DEPTH operands ahead into a rotating set of registers
     mem_ops = []                                    # (pc, macro text)
@@ -597,8 +700,18 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
                 mem_ops.append((pc, "QG_TABLE_SCALED_RAW(%d, %%s)" % (n_tables + list(scaled_tables).index(w1))))
             else:
                 mem_ops.append((pc, "QG_TABLE_RAW(%d, %%s)" % w1))
+    # "x + x" on a cell is MOV acc, T; ADD acc, T: the second operand is the first one's register, which is freed (its next load
+    # issued) after the second use.  Only CONSECUTIVE operands: a register kept across other loads is a live range the allocator pays
+    # for (profiles/r06_call_q_quotient_conversions_ablated.txt)
+    mem_index, merged, deduped = {}, [], []
+    for pc, text in mem_ops:
+        if dedup and merged and merged[-1][1] == text:
+            deduped.append((pc, text % "i"))
+        else:
+            merged.append((pc, text))
+        mem_index[pc] = len(merged) - 1
+    mem_ops = merged
     D = min(PREFETCH_DEPTH, len(mem_ops))
-    mem_index = {pc: j for j, (pc, _) in enumerate(mem_ops)}
     # ---- which "MUL acc, alpha^k ; ADD sum, acc" pairs become terms of a fused dot product: the product's accumulator
     #      must die with the ADD (its next use, if any, is a write)
     def dies_after(acc, pc):
@@ -619,7 +732,8 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
     while True:                                     # constraints whose half-summed value is used in a way the emission cannot express
         try:                                        # go back to plain products, one at a time (plan_wide_constraints)
             out, stats = _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, sync_every, lazy_sub, const_factor, set(scaled_tables),
-                                    plan_wide_constraints(ins, fused, banned, const_factor, min_terms, set(scaled_tables)) if wide_products and FUSE_ALPHA_DOT_PRODUCTS else ({}, {}, {}))
+                                    plan_wide_constraints(ins, fused, banned, const_factor, min_terms, set(scaled_tables), set(small)) if wide_products and FUSE_ALPHA_DOT_PRODUCTS else ({}, {}, {}),
+                                    small)
             break
         except WideViolation as e:
             banned.add(e.k)
@@ -631,6 +745,7 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
     prime = "".join("    m%d = %s;\n" % (j, mem_ops[j][1] % "i32") for j in range(D))
     used = sorted(set(w1 >> 24 for op, _, kind, w1 in ins if op <= OP_MUL and kind == SRC_DERIVED))
     inc = _INC_TEMPLATE % dict(layout=layout, regs=regs, prime=prime, body=body, depth=D, derived_begin=_derived_fallback(derived, used),
+                               small_begin=_SMALL_FALLBACK_BEGIN if stats["baked"] else "", small_end=_SMALL_FALLBACK_END if stats["baked"] else "",
                                derived_end=_DERIVED_FALLBACK_END % "".join("#undef QG_DERIVED_FALLBACK_%d\n" % k for k in used) if used else "",
                                wide=("    QgWide wd;\n" if stats["fused"] else "") + ("    QgWide wq;\n" if stats["wide_terms"] else ""),
                                temp_acc=", acc4 = fl_zero()" if any(d == TEMP_ACC for _, d, _, _ in ins) else "")
@@ -641,6 +756,9 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
           "negated, %d constraints kept plain), %d loads %d ahead, %d reductions -> %s"
           % (layout, len(ins), stats["mul"], stats["mulr"], stats["fused"], stats["flushes"], stats["wide_terms"], stats["wide_closes"], stats["wide_neg"],
              stats["wide_banned"], stats["loads"], D, stats["reduce"], name))
+    if small or dedup:
+        print("   small multiples: %s" % (", ".join("%d x const %d (%d)" % (n, k, small[k][0]) for k, n in sorted(stats["baked"].items())) or "none"))
+        print("   repeated operands: %s" % (", ".join("pc %d %s" % d_ for d_ in deduped) or "none"))
     return dict(stats, inc=name, depth=D)
 
 
@@ -648,12 +766,37 @@ _INC_TEMPLATE = '''// GENERATED by tools/gen_quotient.py - DO NOT EDIT.  The bod
 // operand macros of quotient_gen.h (operand loads issued %(depth)d operands ahead).  Included by the quotient_gen_%(layout)s*.hip
 // wrappers (device) and, with host definitions of the same macros, by tests/cpp/quotient_gen_host_test.cpp, which runs it on
 // the CPU against the oracle's constraint VM.
-%(derived_begin)s    Fl acc0 = fl_zero(), acc1 = fl_zero(), acc2 = fl_zero(), acc3 = fl_zero()%(temp_acc)s;
+%(small_begin)s%(derived_begin)s    Fl acc0 = fl_zero(), acc1 = fl_zero(), acc2 = fl_zero(), acc3 = fl_zero()%(temp_acc)s;
 %(wide)s%(regs)s    uint32_t i32 = (uint32_t)(lane < N ? lane : N - 1);
 %(prime)s    QG_POINT_LOOP_BEGIN
 %(body)s
     QG_POINT_LOOP_END
-%(derived_end)s'''
+%(derived_end)s%(small_end)s'''
+
+
+# A multiple by constant k, whose value the generator knows to be the small integer c (structural_constants), is written as
+# QG_SCALE(k, f, x) [; fl_weak_reduce; QG_RESCALE(f', .) ...] [; QG_NEGSCALED(C, F, .)] with f f' ... = |c| (scale_plan).  The device
+# (quotient_gen.h) takes fl_scale<f>(x), fl_scale<f'>(.) and fl_sub_c<C, F>(0, .) - its launch has checked the constant table against
+# QGenKernel::baked; an includer that does not define the macros (a harness that runs the body on constants of its own choosing) takes
+# the product by the table's constant for the first and nothing for the others: the same value, within the same bounds.
+_SMALL_FALLBACK_BEGIN = '''// QG_SCALE(k, f, x) [QG_RESCALE(f', .) ...] [QG_NEGSCALED(C, F, .)] is x times constant k, a structural small integer +-f f' ... of the
+// layout (tools/gen_quotient.py structural_constants): on the device shifts and adds (quotient_gen.h; the launch first checks the constant
+// table against the kernel table's list).  Where the includer does not define the macros the first is the product by the table's
+// constant and the others do nothing - the same value mod p, normalised.
+#ifndef QG_SCALE
+#define QG_SCALE_FALLBACK
+#define QG_SCALE(k, C, x) fl_mul_r280(x, QG_CONST_R280(k))
+#define QG_RESCALE(C, x) x
+#define QG_NEGSCALED(C, F, x) x
+#endif
+'''
+_SMALL_FALLBACK_END = '''#ifdef QG_SCALE_FALLBACK
+#undef QG_SCALE
+#undef QG_RESCALE
+#undef QG_NEGSCALED
+#undef QG_SCALE_FALLBACK
+#endif
+'''
 
 
 def _small_multiple(expr, k):
@@ -693,14 +836,19 @@ _DERIVED_FALLBACK_END = '''#ifdef QG_DERIVED_FALLBACK
 '''
 
 
-def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, sync_every, SUB_LAZY2, CONST_FACTOR, SCALED, plan):
+def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, sync_every, SUB_LAZY2, CONST_FACTOR, SCALED, plan, small=None):
     """one pass over the (part) program: -> (lines, stats); raises WideViolation"""
     n_instr = len(ins)
     wide_mul, wide_close, wide_struct = plan
     out = []
     emit = out.append
     bound = [1, 1, 1, 1, 1]                        # four accumulators of the program format + the generator's own (TEMP_ACC)
-    stats = {"mul": 0, "mulr": 0, "reduce": 0, "loads": len(mem_ops), "fused": 0, "flushes": 0, "wide_terms": 0, "wide_closes": 0, "wide_neg": 0}
+    stats = {"mul": 0, "mulr": 0, "reduce": 0, "loads": len(mem_ops), "fused": 0, "flushes": 0, "wide_terms": 0, "wide_closes": 0, "wide_neg": 0,
+             "baked": {}}                          # baked: constant -> multiplications by it written as shifts and adds
+    small = small or {}
+    last_use = {}                                  # memory operand -> the last instruction that reads it (repeated operands share one)
+    for pc_, q_ in mem_index.items():
+        last_use[q_] = max(last_use.get(q_, -1), pc_)
     wide = {"acc": None, "terms": 0}               # the one wide (unreduced 64-bit column) accumulator of the alpha dot products in flight
     # the constraint whose products are being summed in the second wide accumulator (wq), and which accumulators / slots hold a
     # part of that constraint's value: k -> the constraint, lin -> whether the register (slot) holds a plain part beside what is in wq
@@ -720,6 +868,51 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
         c, f, nb = {1: (2, 1, 2), 2: (8, 2, 4), 3: (16, 4, 8), 4: (16, 4, 8)}[bound[d]]
         emit("    acc%d = fl_sub_c<%d, %d>(fl_zero(), acc%d);" % (d, c, f, d))
         bound[d] = nb
+
+    NEG_TEMPLATE = {1: (2, 1, 2), 2: (8, 2, 4), 3: (16, 4, 8), 4: (16, 4, 8)}      # fl_sub_c<C, F> by the subtrahend's bound -> the result's
+
+    def small_multiple(k, b, product_cost):
+        """constant k times a value of bound b as shifts and adds, if that is cheaper than the product it replaces: -> scale_plan's
+        (steps, cost, bound), or None.  Priced with the weak reductions the bounds force: inside the plan, before a negation of a
+        bound above 4, and one more for a result above 4 (the next subtraction or negation of it pays that)."""
+        if k not in small:
+            return None
+        plan = scale_plan(small[k][0], b)
+        if plan is None:
+            return None
+        steps, cost, ob = plan
+        if small[k][0] < 0:
+            cost += 9 + (REDUCE_COST if ob > 4 else 0)
+            ob = NEG_TEMPLATE[1 if ob > 4 else ob][2]
+        if ob > 4:
+            cost += REDUCE_COST
+        if cost >= product_cost and os.environ.get("QG_VERBOSE"):
+            print("   stays a product: constant %d (%d) on bound %d, %d >= %d" % (k, small[k][0], b, cost, product_cost))
+        return plan if cost < product_cost else None
+
+    def emit_scaled(k, plan, d, expr):
+        """acc_d = constant k x expr by the plan (its leading reduction, if any, was applied to expr by the caller)"""
+        steps = [st for st in plan[0]]
+        if steps[0] == "R":
+            steps = steps[1:]
+        emit("    acc%d = QG_SCALE(%d, %d, %s);" % (d, k, steps[0], expr))
+        b = plan[3] * steps[0]
+        for st in steps[1:]:
+            if st == "R":
+                bound[d] = b
+                reduce_acc(d)
+                b = 1
+            else:
+                emit("    acc%d = QG_RESCALE(%d, acc%d);" % (d, st, d))
+                b *= st
+        bound[d] = b
+        if small[k][0] < 0:
+            if bound[d] > 4:
+                reduce_acc(d)
+            c_, f_, nb = NEG_TEMPLATE[bound[d]]
+            emit("    acc%d = QG_NEGSCALED(%d, %d, acc%d);" % (d, c_, f_, d))
+            bound[d] = nb
+        stats["baked"][k] = stats["baked"].get(k, 0) + 1
 
     def flush_wide():
         """fold the pending dot product into its accumulator: one Montgomery reduction for all its terms"""
@@ -783,6 +976,7 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
         sm = wacc[src_acc] if src_acc is not None else (wslot.get(w1) if op <= OP_MUL and kind == SRC_SLOT else None)
         dm = wacc[d] if op != OP_MOV else None
         op_e = op                                   # None: nothing to compute; "NEG" / "NEGMOV": the plain part changes sign
+        closed_here = False                         # this MUL takes a constraint's wide sum back: its constant stays a factor
         if op == OP_MOV:
             wacc[d] = dict(sm) if sm else None
             if sm and not sm["lin"]:
@@ -831,6 +1025,7 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
                         wslot[r_] = None
                 wq.update(k=None, units=0, terms=0)
                 stats["wide_closes"] += 1
+                closed_here = True
                 src = ("QG_CONST_R280_UP(%d)" if g > 0 else "QG_CONST_R280_UPN(%d)") % w1
             elif sm or dm:
                 raise WideViolation((sm or dm)["k"], "multiplied at pc %d" % pc)
@@ -936,7 +1131,30 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
                 bound[d] = sb + 1
         elif op_e == OP_MUL:
             tgt = fused.get(pc)
-            if tgt is not None and (wide["acc"] in (None, tgt)):
+            # ---- a small structural multiple instead of the product (structural_constants, scale_plan): "MUL acc, c" scales the
+            #      accumulator, "MOV acc, c; MUL acc, x" the operand.  Priced against what the product would be here: a term of the
+            #      open dot product (whose sum the plain ADD that follows then has to flush: a reduction more), else a product
+            scaling = None
+            if os.environ.get("QG_VERBOSE") and ((kind == SRC_CONST and w1 in small) or (const_before in small and kind != SRC_CONST)):
+                print("   pc %d: small constant, closes a wide sum %s, fused %s, wide open on %s" % (pc, closed_here, tgt, wide["acc"]))
+            if small and not closed_here and src_acc != d:
+                if kind == SRC_CONST and w1 in small:
+                    fused_here = tgt is not None and wide["acc"] in (None, tgt)
+                    against = PRODUCT_COST if not fused_here else WIDE_TERM_COST if wide["acc"] is None else WIDE_TERM_COST - 9 - 104
+                    plan_ = small_multiple(w1, bound[d], against)
+                    if plan_ is not None:
+                        if plan_[0][0] == "R":
+                            reduce_acc(d)
+                        scaling = (w1, plan_ + (bound[d],), v)
+                elif kind != SRC_CONST and const_before is not None and const_before in small and not (kind == SRC_TABLE and w1 in SCALED):
+                    plan_ = small_multiple(const_before, sb, PRODUCT_COST)
+                    if plan_ is not None and not (plan_[0][0] == "R" and src_acc is None):
+                        if plan_[0][0] == "R":
+                            reduce_src()
+                        scaling = (const_before, plan_ + (sb,), src)
+            if scaling is not None:
+                emit_scaled(scaling[0], scaling[1], d, scaling[2])
+            elif tgt is not None and (wide["acc"] in (None, tgt)):
                 # term of a dot product: acc_tgt += v * alpha^k with the reduction deferred.  A multiplicand of bound b (limbs
                 # < b 2^28) adds < 9 b 2^56 to a column: the terms' bounds may sum to DOT_MAX_TERMS before the columns near 2^64
                 if bound[d] > 4:
@@ -1002,7 +1220,7 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
         # this instruction consumed memory operand q and freed register q % D: start the load of operand q + D there - or, in
         # the last D steps of a point, of the next point's operand whose home register that is (operand j lives in m[j % D];
         # when D does not divide the operand count the tail fills the registers in rotated order)
-        if pc in mem_index:
+        if pc in mem_index and last_use[mem_index[pc]] == pc:
             q, L = mem_index[pc], len(mem_ops)
             if q + D < L:
                 issue(q + D, False)
@@ -1062,8 +1280,9 @@ QGenPart quotient_gen_%(layout)s%(suffix)s_p%(part)d() { return QGenPart{%(wgs)d
         f.write(src)
 
 
-def write_kernel_table(layout, suffix, variant, code, n_consts, n_tables, ncols, n_parts, scaled=(), derived=()):
-    """the host-side entry of one variant: what ss_eval_quotient looks up by the program's hash"""
+def write_kernel_table(layout, suffix, variant, code, n_consts, n_tables, ncols, n_parts, scaled=(), derived=(), baked=()):
+    """the host-side entry of one variant: what ss_eval_quotient looks up by the program's hash.  `baked`: (constant, Montgomery image)
+    of every constant some part multiplies by with shifts and adds - the launch compares them with the program's constant table"""
     decl = "".join("QGenPart quotient_gen_%s%s_p%d();\n" % (layout, suffix, j) for j in range(n_parts))
     parts = ", ".join("quotient_gen_%s%s_p%d()" % (layout, suffix, j) for j in range(n_parts))
     src = """// GENERATED by tools/gen_quotient.py - DO NOT EDIT; regenerate with `python tools/gen_quotient.py %(layout)s`.
@@ -1081,14 +1300,18 @@ const QGenKernel &quotient_gen_%(layout)s%(suffix)s() {
     static const uint32_t scaled[] = {%(scaled)s};
     // derived columns the kernels read (tools/gen_quotient.py derived_column_of; built per launch, quotient_derive.h): the trace column,
     // then (row offset, coefficient) per term
+    // constants the kernels hold as code (small structural multiples: tools/gen_quotient.py structural_constants): constant index and the
+    // interchange image it must have - ss_eval_quotient interprets a program whose table says otherwise
+    static const QGenBaked baked[] = {%(baked)s};
     static const QGenKernel k = {"%(layout)s", 0x%(hash)016xull, %(n_instr)du, %(n_consts)du, %(n_tables)du, %(ncols)du, %(variant)du, %(n_parts)du, {%(parts)s},
-                                 %(n_scaled)du, scaled, %(n_derived)du, {%(derived)s}};
+                                 %(n_baked)du, baked, %(n_scaled)du, scaled, %(n_derived)du, {%(derived)s}};
     return k;
 }
 
 }  // namespace ss
 """ % dict(layout=layout, suffix=suffix, variant=variant, n_parts=n_parts, hash=code_hash(code), n_instr=len(code) // 2, n_consts=n_consts,
-           n_tables=n_tables, ncols=ncols, decl=decl, parts=parts, n_scaled=len(scaled), scaled=", ".join("%du" % t for t in scaled) if scaled else "0u", n_derived=len(derived),
+           n_tables=n_tables, ncols=ncols, decl=decl, parts=parts, n_scaled=len(scaled), scaled=", ".join("%du" % t for t in scaled) if scaled else "0u", n_derived=len(derived), n_baked=len(baked),
+           baked=", ".join("{%du, {%s}}" % (c, ", ".join("0x%016xull" % ((v >> (64 * j)) & (2**64 - 1)) for j in range(4))) for c, v in baked) if baked else "{0u, {0, 0, 0, 0}}",
            derived=", ".join("{%du, %du, {%s}, {%s}}" % (col, len(terms), ", ".join("%du" % off for off, _ in terms), ", ".join("%d" % c for _, c in terms))
                              for col, terms in derived))
     with open(os.path.join(OUT_DIR, "quotient_gen_%s%s.hip" % (layout, suffix)), "w") as f:
