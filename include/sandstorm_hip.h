@@ -164,6 +164,15 @@ ss_status ss_lde_fp252(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols,
 ss_status ss_evaluate_fp252(ss_ctx *ctx, const uint64_t *const *d_coeffs, uint32_t ncols, uint32_t log_n,
                             uint32_t log_blowup, const uint64_t offset[4], uint64_t *const *d_evals);
 
+/* Every 2^log_stride-th row of `ncols` columns as contiguous columns: d_out[c][j] = d_in[c][j << log_stride], j < nrows_out, 32-byte
+ * cells.  With an LDE blowup above 2 (`--lde-blowup-factor`, cli/src/main.rs:53-54) the composition constraint, of degree
+ * ce_blowup_factor = 2 (src/lib.rs:110), is still evaluated on the 2n-point coset offset*<w_2n> only: rows j << (log_blowup - 1) of the
+ * LDE, which this call hands to ss_eval_quotient / ss_eval_quotient_rows as columns of log_blowup = 1.  nrows_out is arbitrary (a row
+ * block plus its halo); d_in[c] holds at least ((nrows_out - 1) << log_stride) + 1 cells, d_out[c] nrows_out, and nothing beyond them is
+ * written; the two do not overlap.  log_stride <= 4; any ncols (16 columns a launch).  On the ctx stream, no host sync. */
+ss_status ss_subsample_rows(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride,
+                            uint64_t *const *d_out);
+
 /* ---- (e) ONE transform spread over R = 2^log_ranks GPUs (nothing in the reference to match: its
  * Matrix::interpolate / evaluate run in one address space, src/lib.rs:17-26).  A rank holds the contiguous block
  * [rank n/R, (rank+1) n/R) of the array.  The network's log2(n/R) stages that pair elements less than n/R apart never leave

@@ -87,6 +87,7 @@ SIGNATURES = {
     "ss_ntt_fp252": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint32, C.c_int, _u64p, C.c_int, C.c_int]),
     "ss_lde_fp252": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _vpp, _vpp]),
     "ss_evaluate_fp252": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _vpp]),
+    "ss_subsample_rows": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint64, C.c_uint32, _vpp]),
     "ss_ntt_shard_fp252": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u64p, C.c_int, C.c_uint32, _vpp]),
     "ss_hash_rows": (C.c_int, [C.c_void_p, C.c_int, _vpp, C.c_uint32, C.c_uint64, C.c_void_p]),
     "ss_hash_rows_ex": (C.c_int, [C.c_void_p, C.c_int, _vpp, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]),

@@ -171,6 +171,11 @@ class Context:
         check(self.lib.ss_evaluate_fp252(self.handle, _ptr_array(coeff_cols), len(coeff_cols), log_n, log_blowup,
                                          off, _ptr_array(evals_out)))
 
+    def subsample_rows(self, cols_in, nrows_out, log_stride, cols_out):
+        """ss_subsample_rows: cols_out[c][j] = cols_in[c][j << log_stride], j < nrows_out (the constraint-evaluation coset's rows of a
+        wider LDE)"""
+        check(self.lib.ss_subsample_rows(self.handle, _ptr_array(cols_in), len(cols_in), nrows_out, log_stride, _ptr_array(cols_out)))
+
     def ntt_shard(self, cols, log_n, log_ranks, rank, direction, offset, part, log_expand=0, out=None):
         """ss_ntt_shard_fp252: this rank's share (part LOCAL / CROSS) of ONE transform of 2^log_n points spread over 2^log_ranks ranks"""
         _keep, off = _felt_ptr(offset)

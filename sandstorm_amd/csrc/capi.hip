@@ -968,6 +968,24 @@ ss_status ss_evaluate_fp252(ss_ctx *ctx, const uint64_t *const *d_coeffs, uint32
     return SS_OK;
 }
 
+// Every 2^log_stride-th row of `ncols` columns as columns of their own (include/sandstorm_hip.h): MAX_COLS columns per launch.
+ss_status ss_subsample_rows(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride,
+                            uint64_t *const *d_out) {
+    if (!ctx || !d_in || !d_out) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!ncols || !nrows_out) return fail(SS_ERR_INVALID, "no columns or no rows");
+    if (log_stride > 4) return fail(SS_ERR_INVALID, "log_stride %u > 4", log_stride);
+    if (nrows_out > (1ull << 40)) return fail(SS_ERR_INVALID, "size out of range");
+    if (has_null((const void *const *)d_in, ncols) || has_null((const void *const *)d_out, ncols)) return fail(SS_ERR_INVALID, "NULL column");
+    for (uint32_t base = 0; base < ncols; base += MAX_COLS) {
+        const uint32_t nc = ncols - base < (uint32_t)MAX_COLS ? ncols - base : (uint32_t)MAX_COLS;
+        ColPtrs cols;
+        memset(&cols, 0, sizeof cols);
+        for (uint32_t c = 0; c < nc; ++c) { cols.src[c] = d_in[base + c]; cols.dst[c] = d_out[base + c]; }
+        HIP_TRY(launch_subsample_rows(ctx->stream, cols, nc, nrows_out, log_stride));
+    }
+    return SS_OK;
+}
+
 // One rank's share of ONE transform spread over R = 2^log_ranks ranks (include/sandstorm_hip.h; host/sharded.cpp).
 ss_status ss_ntt_shard_fp252(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n, uint32_t log_ranks, uint32_t rank,
                              int direction, const uint64_t offset[4], int part, uint32_t log_expand, uint64_t *const *d_out) {

@@ -648,6 +648,29 @@ hipError_t launch_deep_rational(hipStream_t st, const void *const *trace, const 
     return hipGetLastError();
 }
 
+// ---- row sub-sampling: out[c][j] = in[c][j << log_stride], j < nrows_out (the constraint-evaluation coset's rows out of a wider
+// LDE's: ss_subsample_rows).  One lane one cell, two 16-byte loads and stores; the stores coalesce, the loads use 32 of every
+// 32 << log_stride bytes
+__global__ __launch_bounds__(256) void subsample_rows_kernel(ColPtrs cols, uint64_t nrows_out, uint32_t log_stride) {
+    const void *in_v = cols.src[0];
+    void *out_v = cols.dst[0];
+#pragma unroll
+    for (int c = 1; c < MAX_COLS; ++c)
+        if (blockIdx.y == (unsigned)c) { in_v = cols.src[c]; out_v = cols.dst[c]; }
+    const Fp *in = reinterpret_cast<const Fp *>(in_v);
+    Fp *out = reinterpret_cast<Fp *>(out_v);
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < nrows_out; j += (uint64_t)gridDim.x * blockDim.x)
+        dstore(out + j, dload(in + (j << log_stride)));
+}
+hipError_t launch_subsample_rows(hipStream_t st, const ColPtrs &cols, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride) {
+    if (nrows_out == 0 || ncols == 0) return hipSuccess;
+    if (ncols > (uint32_t)MAX_COLS) return hipErrorInvalidValue;
+    uint64_t gx = (nrows_out + 255) / 256;
+    if (gx > 65536) gx = 65536;
+    hipLaunchKernelGGL(subsample_rows_kernel, dim3((uint32_t)gx, ncols), dim3(256), 0, st, cols, nrows_out, log_stride);
+    return hipGetLastError();
+}
+
 // gather with a column selector: out[j] = cols[col[j]][idx[j]]
 struct GatherArgs { const Fp *cols[MAX_COLS]; };
 __global__ void gather_cells_kernel(GatherArgs a, const uint32_t *__restrict__ col, const uint64_t *__restrict__ idx,

@@ -124,6 +124,8 @@ hipError_t launch_ood_fold(hipStream_t st, const OodFoldArray *d_arrays, uint32_
                            uint64_t in_len, uint32_t levels, bool canonical);
 hipError_t launch_gather_cells(hipStream_t st, const void *const *cols, uint32_t ncols, const uint32_t *col,
                                const uint64_t *idx, uint32_t n, Fp *out);
+// dst[c][j] = src[c][j << log_stride], j < nrows_out, c < ncols <= MAX_COLS
+hipError_t launch_subsample_rows(hipStream_t st, const ColPtrs &cols, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride);
 
 // ---- ext.hip (extension-trace scans; PermOperand and the scratch sizes are in ext_scan.h)
 struct PermOperand;

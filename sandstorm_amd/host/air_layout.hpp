@@ -77,8 +77,9 @@ private:
     // the program lowered for `ch` with a placeholder composition coefficient, and where its powers sit among the constants
     struct Prepared { bool valid = false; uint64_t n = 0; std::vector<Felt> ch; AirProgramData pd; std::vector<uint32_t> alpha_slot; } prepared_;
 protected:
+    // lb: of the constraint-evaluation coset the tables are built over (Air::log_ce_blowup), not of the LDE
     LayoutAir(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t lb, uint64_t lde_offset)
-        : ctx_(ctx), pi_(pi), log_n_(log_n), lb_(lb), offset_(lde_offset), n_(1ull << log_n), g_(root_of_unity(log_n)) {}
+        : ctx_(ctx), pi_(pi), log_n_(log_n), lb_(lb), offset_(lde_offset), n_(1ull << log_n), g_(root_of_unity(log_n)) { log_ce_blowup = lb; }
     // registers the periodic columns and every table the composition refers to (their set and order do not depend on the
     // challenges), collects the mask, builds the tables on the device when there is one; call at the end of the constructor
     void finish_construction();

@@ -561,8 +561,8 @@ private:
 
 }  // namespace
 
-std::unique_ptr<Air> make_starknet_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_blowup, uint64_t lde_offset) {
-    return std::unique_ptr<Air>(new StarknetAir(ctx, pi, log_n, log_blowup, lde_offset));
+std::unique_ptr<Air> make_starknet_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_ce_blowup, uint64_t lde_offset) {
+    return std::unique_ptr<Air>(new StarknetAir(ctx, pi, log_n, log_ce_blowup, lde_offset));
 }
 
 }  // namespace ssh

@@ -46,6 +46,7 @@ uint32_t ssh_abi_version(void) { return SSH_HOST_ABI_VERSION; }
 void ssh_air_destroy(ssh_air *a) { delete reinterpret_cast<Air *>(a); }
 uint32_t ssh_air_columns(const ssh_air *a, int which) {
     const Air *air = reinterpret_cast<const Air *>(a);
+    if (which == 3) return air->log_ce_blowup;               // of the coset its tables are built over (Air::log_ce_blowup)
     return which == 0 ? air->num_base_columns : which == 1 ? air->num_extension_columns : (uint32_t)air->mask.size();
 }
 
@@ -65,6 +66,7 @@ static int prove_impl(ss_ctx *ctx, ssh_air *air_h, int tree_kind, uint32_t n_fri
             opt.num_queries = options[0]; opt.lde_blowup_factor = options[1]; opt.grinding_factor = options[2];
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
+        lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
         Matrix base;
         base.nrows = 1ull << log_n;
         for (uint32_t c = 0; c < nbase; ++c) base.cols.push_back(d_base[c]);
@@ -185,6 +187,7 @@ static int prove_sharded_impl(ss_ctx *ctx, ssh_air *air_h, int tree_kind, uint32
             opt.num_queries = options[0]; opt.lde_blowup_factor = options[1]; opt.grinding_factor = options[2];
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
+        lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
         std::unique_ptr<Transport> local = lg ? make_local_transport(*lg, rank) : nullptr;
         Transport *comm = lg ? local.get() : reinterpret_cast<Transport *>(rccl);
         if (comm->world != world || comm->rank != rank) throw std::runtime_error("ssh_prove_sharded: the group has another number of ranks, or this is another rank of it");
@@ -392,21 +395,21 @@ static AirPublicInput public_input_from_args(int layout, uint32_t rc_min, uint32
 // The real `recursive` AIR for a public input (air_recursive.cpp).  ctx may be NULL: no device tables are built and the
 // handle only serves ssh_air_dump (host-side checks).
 int ssh_air_create_recursive(ss_ctx *ctx, uint32_t rc_min, uint32_t rc_max, uint64_t n_steps, const uint32_t *segments,
-                             const uint32_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint32_t log_n, uint32_t log_blowup,
+                             const uint32_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint32_t log_n, uint32_t log_ce_blowup,
                              ssh_air **out) {
     try {
         const AirPublicInput pi = public_input_from_args(1, rc_min, rc_max, n_steps, segments, mem_addresses, mem_values, n_mem);
-        *out = reinterpret_cast<ssh_air *>(make_recursive_air(ctx, pi, log_n, log_blowup, 3).release());
+        *out = reinterpret_cast<ssh_air *>(make_recursive_air(ctx, pi, log_n, log_ce_blowup, 3).release());
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }
 // The real `starknet` AIR (air_starknet.cpp); same conventions.
 int ssh_air_create_starknet(ss_ctx *ctx, uint32_t rc_min, uint32_t rc_max, uint64_t n_steps, const uint32_t *segments,
-                            const uint32_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint32_t log_n, uint32_t log_blowup,
+                            const uint32_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint32_t log_n, uint32_t log_ce_blowup,
                             ssh_air **out) {
     try {
         const AirPublicInput pi = public_input_from_args(2, rc_min, rc_max, n_steps, segments, mem_addresses, mem_values, n_mem);
-        *out = reinterpret_cast<ssh_air *>(make_starknet_air(ctx, pi, log_n, log_blowup, 3).release());
+        *out = reinterpret_cast<ssh_air *>(make_starknet_air(ctx, pi, log_n, log_ce_blowup, 3).release());
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }
@@ -539,6 +542,7 @@ int ssh_prove_files(ss_ctx *ctx, int layout, const uint8_t *trace_bin, uint64_t 
             opt.num_queries = options[0]; opt.lde_blowup_factor = options[1]; opt.grinding_factor = options[2];
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
+        lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
         std::mutex m;
         std::condition_variable cv;
         std::vector<uint64_t> ticket(job.ncols, 0);
@@ -658,8 +662,6 @@ int ssh_prove_files_device(ss_ctx *ctx, int layout, const uint8_t *trace_bin, ui
         Air *air = reinterpret_cast<Air *>(air_h);
         if (air->num_base_columns != job.ncols) throw std::runtime_error("ssh_prove_files_device: the AIR is another layout's");
         for (uint32_t c = 0; c < job.ncols; ++c) if (!d_cols[c]) throw std::runtime_error("ssh_prove_files_device: NULL column");
-        job.run_device(ctx, d_cols);
-        const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         Claim claim;
         claim.air = air; claim.tree_kind = tree_kind; claim.n_friendly_layers = n_friendly_layers; claim.coin_kind = coin_kind;
         ProofOptions opt;
@@ -667,6 +669,9 @@ int ssh_prove_files_device(ss_ctx *ctx, int layout, const uint8_t *trace_bin, ui
             opt.num_queries = options[0]; opt.lde_blowup_factor = options[1]; opt.grinding_factor = options[2];
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
+        lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before the files go up and the generator writes d_cols
+        job.run_device(ctx, d_cols);
+        const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         Matrix base;
         base.nrows = job.n;
         for (uint32_t c = 0; c < job.ncols; ++c) base.cols.push_back(d_cols[c]);
@@ -706,6 +711,7 @@ ClaimArgs unpack_claim(ssh_air *air_h, int tree_kind, uint32_t n_friendly_layers
         a.opt.num_queries = options[0]; a.opt.lde_blowup_factor = options[1]; a.opt.grinding_factor = options[2];
         a.opt.fri_folding_factor = options[3]; a.opt.fri_max_remainder_coeffs = options[4];
     }
+    lde_log_blowup(a.opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
     memcpy(a.seed.data(), seed, 32);
     return a;
 }

@@ -20,6 +20,13 @@ static uint32_t log2u(uint64_t v) {
     return l;
 }
 
+uint32_t lde_log_blowup(const ProofOptions &opt) {
+    const uint32_t f = opt.lde_blowup_factor;
+    if (f != 2 && f != 4 && f != 8 && f != 16)
+        throw std::runtime_error("the LDE blowup factor must be 2, 4, 8 or 16 (got " + std::to_string(f) + ")");
+    return log2u(f);
+}
+
 // ------------------------------------------------------------------ device objects
 DeviceBuffer::DeviceBuffer(ss_ctx *ctx, size_t bytes) : ctx_(ctx), bytes_(bytes) { ok(ss_dev_alloc(ctx, bytes, &ptr_)); }
 DeviceBuffer::~DeviceBuffer() { if (ptr_) ss_dev_free(ctx_, ptr_); }
@@ -216,8 +223,11 @@ void fri_open_from(ss_ctx *ctx, const Conventions &conv, const ProofOptions &opt
 Proof Prover::prove(const Digest &coin_seed, const Matrix &base_trace, const ExtensionBuilder &build_extension) {
     Air &air = *claim_.air;
     const uint64_t n = base_trace.nrows;
-    const uint32_t log_n = log2u(n), lb = log2u(opt_.lde_blowup_factor), log_N = log_n + lb;
+    const uint32_t lb = lde_log_blowup(opt_), log_n = log2u(n), log_N = log_n + lb;
     const uint64_t N = n << lb;
+    const uint32_t ncomp = conv_.composition_columns;
+    if (ncomp != 2) throw std::runtime_error("composition split implemented for two composition columns");
+    if (air.log_ce_blowup != 1) throw std::runtime_error("the AIR's tables must be built for the constraint-evaluation blowup 2 (log_ce_blowup = 1), whatever the LDE blowup factor");
     const Felt g = felt_from_u64(conv_.lde_offset);
     PublicCoin coin(claim_.coin_kind, coin_seed);
     Proof proof;
@@ -284,8 +294,10 @@ Proof Prover::prove(const Digest &coin_seed, const Matrix &base_trace, const Ext
         coeff_cols.insert(coeff_cols.end(), ext_co.cols.begin(), ext_co.cols.end());
     }
 
-    // 5. composition constraint on the LDE domain; its coefficients in bit-reversed order split
-    //    for free into H0 (first half) and H1 (second half)
+    // 5. composition constraint on the constraint-evaluation coset g * <w_2n> - the constraints have degree 2, so H has 2n
+    //    coefficients whatever the LDE blowup is: the LDE domain itself at blowup 2, every 2^(lb-1)-th row of it above (as contiguous
+    //    columns: the constraint kernels and the AIR's tables then run as at blowup 2); its 2n coefficients in bit-reversed order
+    //    split for free into H0 (first half) and H1 (second half)
     proof.composition_coeff = coin.draw();
     AirProgramData pd = air.build_program(n, proof.challenges, proof.composition_coeff);
     std::vector<uint64_t> consts = flat(pd.program.consts);
@@ -295,13 +307,18 @@ Proof Prover::prove(const Digest &coin_seed, const Matrix &base_trace, const Ext
     prog.d_tables = pd.d_tables; prog.table_desc = pd.table_desc.data(); prog.n_tables = (uint32_t)(pd.table_desc.size() / 2);
     prog.n_slots = pd.program.n_slots;
     mark("program build");
-    DeviceBuffer comp_evals(ctx_, 32 * N);
-    ok(ss_eval_quotient(ctx_, &prog, (const uint64_t *const *)lde_cols.data(), (uint32_t)lde_cols.size(), log_n, lb, g.data(), comp_evals.u64()));
+    DeviceBuffer comp_evals(ctx_, 32 * 2 * n);
+    if (lb == 1) {
+        ok(ss_eval_quotient(ctx_, &prog, (const uint64_t *const *)lde_cols.data(), (uint32_t)lde_cols.size(), log_n, 1, g.data(), comp_evals.u64()));
+    } else {
+        Matrix ce_cols = Matrix::alloc(ctx_, (uint32_t)lde_cols.size(), 2 * n);      // freed before the composition LDE is allocated (the pool is stream-ordered)
+        ok(ss_subsample_rows(ctx_, (const uint64_t *const *)lde_cols.data(), (uint32_t)lde_cols.size(), 2 * n, lb - 1, ce_cols.cols.data()));
+        mark("subsample");
+        ok(ss_eval_quotient(ctx_, &prog, (const uint64_t *const *)ce_cols.cols.data(), ce_cols.num_cols(), log_n, 1, g.data(), comp_evals.u64()));
+    }
     mark("quotient");
     uint64_t *ce = comp_evals.u64();
-    ok(ss_ntt_fp252(ctx_, &ce, 1, log_N, SS_NTT_INVERSE, g.data(), SS_ORDER_NATURAL, SS_ORDER_BITREV));
-    const uint32_t ncomp = conv_.composition_columns;
-    if (ncomp != (1u << lb) || ncomp != 2) throw std::runtime_error("composition split implemented for blowup 2");
+    ok(ss_ntt_fp252(ctx_, &ce, 1, log_n + 1, SS_NTT_INVERSE, g.data(), SS_ORDER_NATURAL, SS_ORDER_BITREV));
     std::vector<uint64_t *> comp_coeffs;
     for (uint32_t k = 0; k < ncomp; ++k) comp_coeffs.push_back(ce + 4 * n * k);
     Matrix comp_lde = Matrix::alloc(ctx_, ncomp, N);

@@ -25,6 +25,10 @@ struct ProofOptions {                   // cli/src/main.rs:51-60 defaults
     uint32_t fri_max_remainder_coeffs = 16;
 };
 
+// log2 of the LDE blowup factor the provers of the 252-bit field accept - 2, 4, 8 or 16 (`--lde-blowup-factor`, cli/src/main.rs:53-54);
+// throws for any other value, naming the set
+uint32_t lde_log_blowup(const ProofOptions &opt);
+
 struct Conventions {                    // ministark-internal, SURVEY.md Appendix A
     uint64_t lde_offset = 3;            // M2
     uint32_t composition_columns = 2;   // M5
@@ -117,6 +121,9 @@ public:
     virtual ~Air() = default;
     std::string name;
     uint32_t num_base_columns = 0, num_extension_columns = 0, num_challenges = 0;
+    // the coset the program's tables are laid out for: offset * <w_(n << log_ce_blowup)>.  The constraints have degree 2
+    // (ce_blowup_factor, src/lib.rs:110), so the provers evaluate them on 2n points whatever the LDE blowup is and want 1 here
+    uint32_t log_ce_blowup = 1;
     std::vector<std::pair<uint32_t, uint32_t>> mask;     // trace_arguments(): sorted (column, offset)
     virtual AirProgramData build_program(uint64_t n, const std::vector<Felt> &challenges, const Felt &composition_coeff) = 0;
     // Optional, ahead of build_program: everything of the program that the challenges decide (its code, every constant but the powers
@@ -221,8 +228,10 @@ private:
 // the layouts' AIRs
 struct AirPublicInput;
 // the real `recursive` layout (air_recursive.cpp; mirror of sandstorm_amd/layouts/recursive.py)
-std::unique_ptr<Air> make_recursive_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_blowup, uint64_t lde_offset);
-std::unique_ptr<Air> make_starknet_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_blowup, uint64_t lde_offset);
+// log_ce_blowup: of the CONSTRAINT-EVALUATION coset the periodic and inverse tables are built over (Air::log_ce_blowup) - 1 for a
+// prover at any LDE blowup factor (ProofOptions::lde_blowup_factor is not this); other values serve direct ss_eval_quotient calls
+std::unique_ptr<Air> make_recursive_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_ce_blowup, uint64_t lde_offset);
+std::unique_ptr<Air> make_starknet_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_ce_blowup, uint64_t lde_offset);
 std::vector<uint64_t> layout_air_tables(const Air &air);         // table descriptions of a layout AIR (host-side checks)
 
 }  // namespace ssh

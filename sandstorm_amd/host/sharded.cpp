@@ -556,9 +556,16 @@ bool ShardedProver::prove(const Digest &coin_seed, const std::map<uint32_t, uint
     Air &air = *claim_.air;
     const uint32_t R = comm_.world, r = comm_.rank;
     if (R & (R - 1)) throw std::runtime_error("the row blocks need a power-of-two number of ranks");
-    const uint32_t log_n = log2u(n), lb = log2u(opt_.lde_blowup_factor), log_N = log_n + lb;
+    const uint32_t lb = lde_log_blowup(opt_), log_n = log2u(n), log_N = log_n + lb;
     const uint64_t N = n << lb, B = N / R;
     if (N % R || n / R < 1) throw std::runtime_error("more ranks than trace rows");
+    const uint32_t ncomp = conv_.composition_columns;
+    if (ncomp != 2) throw std::runtime_error("composition split implemented for two composition columns");
+    if (air.log_ce_blowup != 1) throw std::runtime_error("the AIR's tables must be built for the constraint-evaluation blowup 2 (log_ce_blowup = 1), whatever the LDE blowup factor");
+    // the constraint-evaluation coset g * <w_2n> is every ce_stride-th row of the LDE; this rank's block of it starts at LDE row r B
+    const uint32_t log_ce_stride = lb - 1;
+    const uint64_t ce_stride = 1ull << log_ce_stride, ce_B = 2 * n / R;
+    if (B % ce_stride || (r * B) % ce_stride) throw std::runtime_error("a row block does not start on a row of the constraint-evaluation coset: fewer ranks for this blowup");
     const Felt g = felt_from_u64(conv_.lde_offset);
     const int order = conv_.bitrev_commit ? SS_ORDER_BITREV : SS_ORDER_NATURAL;
     const uint32_t nb = air.num_base_columns, ne = air.num_extension_columns;
@@ -681,16 +688,30 @@ bool ShardedProver::prove(const Digest &coin_seed, const std::map<uint32_t, uint
     prog.consts = consts.data(); prog.n_consts = (uint32_t)pd.program.consts.size();
     prog.d_tables = pd.d_tables; prog.table_desc = pd.table_desc.data(); prog.n_tables = (uint32_t)(pd.table_desc.size() / 2);
     prog.n_slots = pd.program.n_slots;
-    Buf q_block = std::make_shared<DeviceBuffer>(ctx_, 32 * B);
-    if (R == 1) ok(ss_eval_quotient(ctx_, &prog, block_ptrs.data(), (uint32_t)block_ptrs.size(), log_n, lb, g.data(), q_block->u64()));
-    else ok(ss_eval_quotient_rows(ctx_, &prog, block_ptrs.data(), (uint32_t)block_ptrs.size(), log_n, lb, g.data(), r * B, B, B + halo, q_block->u64()));
-    const uint32_t ncomp = conv_.composition_columns;
-    if (ncomp != (1u << lb) || ncomp != 2) throw std::runtime_error("composition split implemented for blowup 2");
-    // the N coefficients in bit-reversed order: positions < n are H0's (in its own bit-reversed order), the rest H1's - the split
+    // (the constraints have degree 2: H has 2n coefficients whatever the LDE blowup is.  Above blowup 2 the block's rows on the
+    // coset - every ce_stride-th, halo included - become contiguous columns, and kernels and tables run as at blowup 2)
+    Buf q_block = std::make_shared<DeviceBuffer>(ctx_, 32 * ce_B);
+    {
+        const uint64_t ce_halo = halo >> log_ce_stride;          // max offset << 1, or the rest of the 2n-point domain
+        std::vector<Buf> ce_blocks;
+        std::vector<const uint64_t *> ce_ptrs = block_ptrs;
+        if (lb > 1) {
+            std::vector<uint64_t *> out_ptrs;
+            for (size_t c = 0; c < block_ptrs.size(); ++c) {
+                ce_blocks.push_back(std::make_shared<DeviceBuffer>(ctx_, 32 * (ce_B + ce_halo)));
+                out_ptrs.push_back(ce_blocks.back()->u64());
+                ce_ptrs[c] = ce_blocks.back()->u64();
+            }
+            ok(ss_subsample_rows(ctx_, block_ptrs.data(), (uint32_t)block_ptrs.size(), ce_B + ce_halo, log_ce_stride, out_ptrs.data()));
+        }
+        if (R == 1) ok(ss_eval_quotient(ctx_, &prog, ce_ptrs.data(), (uint32_t)ce_ptrs.size(), log_n, 1, g.data(), q_block->u64()));
+        else ok(ss_eval_quotient_rows(ctx_, &prog, ce_ptrs.data(), (uint32_t)ce_ptrs.size(), log_n, 1, g.data(), (r * B) >> log_ce_stride, ce_B, ce_B + ce_halo, q_block->u64()));
+    }
+    // the 2n coefficients in bit-reversed order: positions < n are H0's (in its own bit-reversed order), the rest H1's - the split
     // is free, and rank r's block of the array is one of the two halves' blocks 2 r', 2 r' + 1: one exchange deals them out
     std::vector<Buf> comp_coeff_blocks;
     {
-        std::vector<Buf> cb = spread_inverse({q_block}, log_N, &g);
+        std::vector<Buf> cb = spread_inverse({q_block}, log_n + 1, &g);
         q_block.reset();
         if (R == 1) {
             for (uint32_t k = 0; k < ncomp; ++k) {

@@ -106,7 +106,9 @@ def register_air_kind(kind, factory):
 
 
 class HostAir:
-    def __init__(self, ctx, kind, log_n, log_blowup=1):
+    def __init__(self, ctx, kind, log_n, log_ce_blowup=1):
+        # log_ce_blowup: of the coset the AIR's tables are built over - the CONSTRAINT-EVALUATION one, 2n points (1) for a prover at
+        # any ProofOptions.lde_blowup_factor (the constraints have degree 2); never the LDE's
         self.ctx, self.h = ctx, C.c_void_p()        # ctx=None: host-only handle (verification; no device tables)
         load()
         if kind not in _AIR_FACTORIES:
@@ -115,6 +117,11 @@ class HostAir:
         self.num_base_columns = load().ssh_air_columns(self.h, 0)
         self.num_extension_columns = load().ssh_air_columns(self.h, 1)
         self.mask_size = load().ssh_air_columns(self.h, 2)
+        self.log_ce_blowup = load().ssh_air_columns(self.h, 3)
+        if self.log_ce_blowup != log_ce_blowup:
+            self.close()
+            raise _lib.SandstormHipError("host: the AIR of kind %r has its tables over the coset of log_ce_blowup = %d, not %d"
+                                         % (kind, self.log_ce_blowup, log_ce_blowup))
 
     def close(self):
         if self.h:
@@ -124,20 +131,23 @@ class HostAir:
 
 class RecursiveHostAir(HostAir):
     """the C++ host's real `recursive` AIR for a public input (sandstorm_amd/host/air_recursive.cpp).  ctx=None: no device
-    tables, only dump() works (host-side checks)."""
+    tables, only dump() works (host-side checks).  log_ce_blowup: of the coset the periodic and inverse tables are built over - the
+    constraint-evaluation coset of 2n points (1) for a prover at ANY ProofOptions.lde_blowup_factor, since the provers evaluate the
+    degree-2 constraints there and extend the composition columns afterwards; another value only serves direct eval_quotient calls."""
     create = "ssh_air_create_recursive"
     column_tag = "pedersen"                 # what layouts.recursive.Tables calls its periodic columns
 
-    def __init__(self, ctx, pi, log_n, log_blowup=1):
+    def __init__(self, ctx, pi, log_n, log_ce_blowup=1):
         segs, addrs, vals = _public_input_args(pi)
         h = C.c_void_p()
         _check(getattr(load(), self.create)(ctx.handle if ctx is not None else None, pi.rc_min, pi.rc_max, pi.n_steps,
                                                segs.ctypes.data_as(C.POINTER(C.c_uint32)), addrs.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                               vals.ctypes.data_as(C.POINTER(C.c_uint64)), len(addrs), log_n, log_blowup, C.byref(h)))
+                                               vals.ctypes.data_as(C.POINTER(C.c_uint64)), len(addrs), log_n, log_ce_blowup, C.byref(h)))
         self.ctx, self.h = ctx, h
         self.num_base_columns = load().ssh_air_columns(h, 0)
         self.num_extension_columns = load().ssh_air_columns(h, 1)
         self.mask_size = load().ssh_air_columns(h, 2)
+        self.log_ce_blowup = load().ssh_air_columns(h, 3)
 
     def prepare(self, n, challenges):
         """Air::prepare_program: lower the program for these challenges ahead of the composition coefficient"""
@@ -219,7 +229,7 @@ def prover_air(host_air):
         d_tables = int(words[o])
         return _HostProgram(code, consts, n_slots), (_DevicePointer(d_tables) if d_tables else None), desc
     return Air(type(host_air).__name__, host_air.num_base_columns, host_air.num_extension_columns, h.ssh_air_num_challenges(host_air.h), mask,
-               build_program)
+               build_program, log_ce_blowup=host_air.log_ce_blowup)
 
 
 class _DevicePointer:

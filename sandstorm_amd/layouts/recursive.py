@@ -971,15 +971,17 @@ def tables_for(n, blowup=2, offset=3, L=None):
     return _TABLES[key]
 
 
-def make_air(ctx, public_input, n, log_blowup=1, lde_offset=3, L=None):
+def make_air(ctx, public_input, n, log_ce_blowup=1, lde_offset=3, L=None):
     """-> prover.Air for this public input and trace length.  The tables are built once: the periodic ones on the host
-    (up to 2^16 entries each), the full-length inverse tables on the device (ss_inverse_table)."""
+    (up to 2^16 entries each), the full-length inverse tables on the device (ss_inverse_table).  log_ce_blowup: of the coset the tables
+    are laid out over - the CONSTRAINT-EVALUATION one, 2n points (1), for a prover at any ProofOptions.lde_blowup_factor; never the LDE's
+    (prover.Air.log_ce_blowup; the provers refuse another value)."""
     import sys
     from .. import backend as be
     from ..coin import canonical
     from ..prover import Air
     L = L or sys.modules[__name__]
-    tables = tables_for(n, 1 << log_blowup, lde_offset, L)
+    tables = tables_for(n, 1 << log_ce_blowup, lde_offset, L)
     lengths = [tables.length(s) for s in tables.specs]
     desc, off = [], 0
     for ln in lengths:
@@ -990,7 +992,7 @@ def make_air(ctx, public_input, n, log_blowup=1, lde_offset=3, L=None):
     for spec, ln, start in zip(tables.specs, lengths, desc[0::2]):
         view = be.DeviceView(buf, 32 * start, 32 * ln)
         if spec[0] == "inverse":
-            ctx.inverse_table((n << log_blowup).bit_length() - 1, g, be.felt(pow(tables.g, spec[1], P)), view)
+            ctx.inverse_table((n << log_ce_blowup).bit_length() - 1, g, be.felt(pow(tables.g, spec[1], P)), view)
         else:
             import numpy as np
             host = np.stack([be.felt(v) for v in tables.host_values(spec)])
@@ -1006,10 +1008,11 @@ def make_air(ctx, public_input, n, log_blowup=1, lde_offset=3, L=None):
 
     air = Air(L.__name__.rsplit(".", 1)[-1], L.NUM_BASE_COLUMNS, L.NUM_EXTENSION_COLUMNS, 6, L.mask(), build_program)
     air.table_buffer = buf
+    air.log_ce_blowup = log_ce_blowup
     return air
 
 
-def verifier_air(public_input, log_blowup=1, lde_offset=3, L=None):
+def verifier_air(public_input, log_ce_blowup=1, lde_offset=3, L=None):
     """-> verifier.VerifierAir: the same composition, with the tables' underlying functions evaluated at the
     out-of-domain point"""
     import sys
@@ -1017,10 +1020,10 @@ def verifier_air(public_input, log_blowup=1, lde_offset=3, L=None):
     L = L or sys.modules[__name__]
 
     def comp(n, challenges, alpha):
-        return L.composition(n, L.Hints.from_public_input(public_input, challenges, n), challenges, alpha, tables_for(n, 1 << log_blowup, lde_offset, L))
+        return L.composition(n, L.Hints.from_public_input(public_input, challenges, n), challenges, alpha, tables_for(n, 1 << log_ce_blowup, lde_offset, L))
 
     def table_at(n, x, t):
-        tables = tables_for(n, 1 << log_blowup, lde_offset, L)
+        tables = tables_for(n, 1 << log_ce_blowup, lde_offset, L)
         return tables.value_at(tables.specs[t], x)
     return VerifierAir(L.NUM_BASE_COLUMNS, L.NUM_EXTENSION_COLUMNS, 6, L.mask(), comp, table_at)
 

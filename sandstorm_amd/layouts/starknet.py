@@ -1194,16 +1194,16 @@ def mask(hints=None):
 
 
 # ---- the layout as the prover and the verifier see it -------------------------------------------------------------------
-def make_air(ctx, public_input, n, log_blowup=1, lde_offset=3):
+def make_air(ctx, public_input, n, log_ce_blowup=1, lde_offset=3):
     """-> prover.Air (the tables: 9 periodic columns and the periodic multipliers from the host, 5 full-length inverse
     tables built on the device)"""
     import sys
-    return rec.make_air(ctx, public_input, n, log_blowup, lde_offset, sys.modules[__name__])
+    return rec.make_air(ctx, public_input, n, log_ce_blowup, lde_offset, sys.modules[__name__])
 
 
-def verifier_air(public_input, log_blowup=1, lde_offset=3):
+def verifier_air(public_input, log_ce_blowup=1, lde_offset=3):
     import sys
-    return rec.verifier_air(public_input, log_blowup, lde_offset, sys.modules[__name__])
+    return rec.verifier_air(public_input, log_ce_blowup, lde_offset, sys.modules[__name__])
 
 
 def trace_columns(ctx, base_cols_device, n):

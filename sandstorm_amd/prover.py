@@ -8,7 +8,8 @@ Mirrors the default body of ministark's `Stark::prove` as Sandstorm drives it
   3 draw the AIR's challenges, build the extension columns  [A2: caller callback]
   4 LDE of the extension columns, commit, reseed
   5 draw the composition coefficient, evaluate the composition constraint on the
-    LDE domain (Q1), interpolate, split into 2 columns, LDE, commit, reseed (Q2)
+    2n-point constraint-evaluation coset (Q1; the LDE domain itself at blowup 2),
+    interpolate, split into 2 columns, LDE, commit, reseed (Q2)
   6 draw z, out-of-domain evaluations of every mask cell and of the composition
     columns at z^2, reseed
   7 DEEP coefficients (powers of one alpha, src/lib.rs:102-116), DEEP composition
@@ -70,6 +71,9 @@ class Air:
     mask: List[tuple]                   # trace_arguments(): sorted (column, row offset) cells
     # (n, challenges, composition_coeff) -> (air_program.Program, tables uint64[*,4] or None, table_desc list)
     build_program: Callable = None
+    # of the coset build_program's tables are laid out over: offset * <w_(n << log_ce_blowup)>.  The constraints have degree 2, so the
+    # provers evaluate them on 2n points whatever ProofOptions.lde_blowup_factor is, and want 1 here (host/prover.hpp Air::log_ce_blowup)
+    log_ce_blowup: int = 1
 
 
 @dataclass
@@ -129,6 +133,13 @@ def _log2(v):
     return v.bit_length() - 1
 
 
+def lde_log_blowup(options):
+    """log2 of the LDE blowup factor the provers of the 252-bit field accept (host/prover.cpp lde_log_blowup)"""
+    if options.lde_blowup_factor not in (2, 4, 8, 16):
+        raise ValueError("the LDE blowup factor must be 2, 4, 8 or 16 (got %r)" % (options.lde_blowup_factor,))
+    return _log2(options.lde_blowup_factor)
+
+
 def _pow_limbs(base_limbs, count):
     """[alpha^0 .. alpha^(count-1)] as Montgomery limbs (tiny host arithmetic on transcript values)"""
     a = canonical(base_limbs)
@@ -154,8 +165,14 @@ class Prover:
         ctx, opt, conv, air = self.ctx, self.options, self.conv, self.claim.air
         Tree = self.claim.tree
         n = base_trace.nrows
-        log_n, lb = _log2(n), _log2(opt.lde_blowup_factor)
+        lb = lde_log_blowup(opt)
+        log_n = _log2(n)
         log_N, N = log_n + lb, n << lb
+        ncomp = conv.composition_columns
+        assert ncomp == 2, "composition split implemented for two composition columns"
+        if air.log_ce_blowup != 1:
+            raise ValueError("the AIR's tables must be built for the constraint-evaluation blowup 2 (log_ce_blowup = 1), whatever the LDE "
+                             "blowup factor (got log_ce_blowup = %r)" % (air.log_ce_blowup,))
         g = be.felt(conv.lde_offset)
         coin = PublicCoin(self.claim.coin_kind, coin_seed)
         proof = Proof(opt, n, tree_kind=Tree.tree_kind)
@@ -194,7 +211,8 @@ class Prover:
             coeff_cols += ext_coeffs.cols
 
         mark("ext_lde_commit")
-        # 5. composition constraint over the LDE domain, then its 2-column LDE
+        # 5. composition constraint over the constraint-evaluation coset g * <w_2n> (degree-2 constraints: H has 2n coefficients
+        # whatever the LDE blowup is; air.build_program's tables are laid out for that coset), then its 2-column LDE
         comp_coeff = coin.draw()
         proof.composition_coeff = comp_coeff
         program, tables, table_desc = air.build_program(n, challenges, comp_coeff)
@@ -203,14 +221,22 @@ class Prover:
         else:
             d_tables = ctx.column(tables) if len(tables) else None
         mark("lower_program")
-        comp_evals = ctx.alloc(32 * N)
-        ctx.eval_quotient(program, d_tables, table_desc, lde_cols, log_n, lb, g, comp_evals)
+        comp_evals = ctx.alloc(32 * 2 * n)
+        if lb == 1:
+            ce_cols = lde_cols
+        else:
+            # The coset is every 2^(lb-1)-th row of the LDE.  The C++ hosts copy those rows out (ss_subsample_rows); this mirror
+            # evaluates the kept coefficient columns there instead, with a call both of its backends have: the same polynomials at
+            # the same points, so the same values by definition - and no row of the LDE is taken on trust.
+            ce = be.Matrix.empty(ctx, len(coeff_cols), 2 * n)
+            ctx.evaluate(coeff_cols, log_n, 1, g, ce.cols)
+            ce_cols = ce.cols
+        ctx.eval_quotient(program, d_tables, table_desc, ce_cols, log_n, 1, g, comp_evals)
         mark("quotient")
         # coefficients of H in bit-reversed order: the first half is H0 (even coefficients),
         # the second half H1 (odd), each again bit-reversed — the split is free
-        ctx.ntt([comp_evals], log_N, be.INVERSE, g, be.NATURAL, be.BITREV)
-        ncomp = conv.composition_columns
-        assert ncomp == 1 << lb == 2, "composition split implemented for blowup 2"
+        ctx.ntt([comp_evals], log_n + 1, be.INVERSE, g, be.NATURAL, be.BITREV)
+        ce = ce_cols = None
         comp_coeffs = [be.DeviceView(comp_evals, 32 * n * k, 32 * n) for k in range(ncomp)]
         comp_lde = be.Matrix.empty(ctx, ncomp, N)
         ctx.evaluate(comp_coeffs, log_n, lb, g, comp_lde.cols)
