@@ -257,7 +257,9 @@ enum {
     SS_OP_MUL = 4,   /* acc[d] = acc[d] * src   */
     SS_OP_INV = 5,   /* acc[d] = 1 / acc[d]  (0 -> 0), operand ignored */
     SS_OP_ST = 6,    /* slot[payload] = acc[d]  */
-    SS_OP_OUT = 7    /* out[i] = acc[d]         */
+    SS_OP_OUT = 7,   /* out[i] = acc[d]         */
+    SS_OP_CHECK = 10 /* check k = payload: acc[d] must be zero if this row is in domain k (ss_check_constraints only;
+                        ss_eval_quotient and ss_eval_quotient_rows refuse it; 8 and 9 are taken inside the library) */
 };
 enum {
     SS_SRC_ACC = 0,    /* payload = accumulator index                                  */
@@ -298,6 +300,24 @@ ss_status ss_eval_quotient(ss_ctx *ctx, const ss_air_program *prog, const uint64
 ss_status ss_eval_quotient_rows(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_col_blocks,
                                 uint32_t ncols, uint32_t log_n, uint32_t log_blowup, const uint64_t offset[4],
                                 uint64_t row0, uint64_t nrows, uint64_t block_rows, uint64_t *d_out);
+
+/* ---- a trace against its AIR, constraint by constraint (ministark runs `validate_constraints` over the trace in debug builds,
+ *      before it commits to anything).  The program has one SS_OP_CHECK k per constraint and no SS_OP_OUT: the code in front of a
+ * CHECK leaves that constraint's NUMERATOR in the accumulator.  It runs once per row r of the TRACE domain (x = w_n^r, no blowup, no
+ * offset; d_cols are the n-row trace columns, SS_SRC_TRACE reads cols[col][(r + row_offset) mod n], a table is indexed by r mod its
+ * length - a periodic column's table is its values over one period).  A domain is the pair of zerofier factor lists the AIRs use,
+ * factor (p, e) = X^p - w_n^e: row r belongs to it iff some `den` factor vanishes at w_n^r and no `num` factor does, and a factor
+ * vanishes iff p r = e (mod n).  On return first_row_out[k] = the smallest row of domain k at which numerator k is not zero
+ * (UINT64_MAX: the constraint holds) and count_out[k] = the number of such rows; both are host arrays of n_checks entries.
+ * Every check index below n_checks must appear exactly once. */
+#define SS_CHECK_MAX_FACTORS 16u
+typedef struct ss_check_domain {
+    uint32_t n_num, n_den;                       /* <= SS_CHECK_MAX_FACTORS each */
+    uint64_t num[SS_CHECK_MAX_FACTORS][2];       /* (p, e) */
+    uint64_t den[SS_CHECK_MAX_FACTORS][2];
+} ss_check_domain;
+ss_status ss_check_constraints(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n,
+                               const ss_check_domain *domains, uint32_t n_checks, uint64_t *first_row_out, uint32_t *count_out);
 
 /* ---- D1: out-of-domain evaluations + DEEP composition (ministark
  *      DeepPolyComposer, un-vendored; coefficient rule src/lib.rs:102-116).

@@ -38,6 +38,15 @@ class AirProgram(C.Structure):
                 ("n_tables", C.c_uint32), ("n_slots", C.c_uint32)]
 
 
+CHECK_MAX_FACTORS = 16          # SS_CHECK_MAX_FACTORS
+OP_CHECK = 10                   # SS_OP_CHECK
+
+
+class CheckDomain(C.Structure):
+    """ss_check_domain"""
+    _fields_ = [("n_num", C.c_uint32), ("n_den", C.c_uint32), ("num", (C.c_uint64 * 2) * CHECK_MAX_FACTORS), ("den", (C.c_uint64 * 2) * CHECK_MAX_FACTORS)]
+
+
 class GatherJob(C.Structure):
     """ss_gather_job"""
     _fields_ = [("d_cols", C.POINTER(C.c_void_p)), ("ncols", C.c_uint32), ("entry_bytes", C.c_uint32), ("idx", C.POINTER(C.c_uint64)),
@@ -134,6 +143,7 @@ SIGNATURES = {
                                    C.c_uint32, _u64p, C.c_void_p]),
     "ss_eval_quotient_rows": (C.c_int, [C.c_void_p, C.POINTER(AirProgram), _vpp, C.c_uint32, C.c_uint32,
                                         C.c_uint32, _u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "ss_check_constraints": (C.c_int, [C.c_void_p, C.POINTER(AirProgram), _vpp, C.c_uint32, C.c_uint32, C.POINTER(CheckDomain), C.c_uint32, _u64p, _u32p]),
     "ss_deep_compose_rows": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, _vpp, C.c_uint32, C.c_uint32, C.c_uint32,
                                        _u64p, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, _u64p, C.c_uint64, C.c_uint64, C.c_void_p]),

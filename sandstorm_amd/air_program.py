@@ -19,6 +19,7 @@ X^(n/k) zerofier inverses (both periodic in the LDE index) are TABLE operands.
 
 class OP:
     MOV, ADD, SUB, RSUB, MUL, INV, ST, OUT = range(8)
+    CHECK = 10          # SS_OP_CHECK: ss_check_constraints only (payload = the check's index)
 
 
 class SRC:

@@ -403,6 +403,23 @@ class Context:
         check(self.lib.ss_eval_quotient_rows(self.handle, C.byref(prog), _ptr_array(col_blocks), len(col_blocks), log_n,
                                              log_blowup, op, row0, nrows, block_rows, _ptr_of(out)))
 
+    def check_constraints(self, program, tables, table_desc, cols, log_n, domains):
+        """ss_check_constraints: the trace columns `cols` (n = 2^log_n rows, the trace domain) against a program with one CHECK k per
+        constraint; domains[k] = (num, den), lists of zerofier factors (p, e) = X^p - g^e.  -> (first_row uint64[n_checks] with
+        2^64 - 1 where constraint k holds, count uint32[n_checks])"""
+        prog, _keep = _air_program(program, tables, table_desc)
+        doms = (_lib.CheckDomain * max(1, len(domains)))()
+        for k, (num, den) in enumerate(domains):
+            doms[k].n_num, doms[k].n_den = len(num), len(den)
+            for fs, dst in ((num, doms[k].num), (den, doms[k].den)):
+                for j, (p_, e) in enumerate(fs[:_lib.CHECK_MAX_FACTORS]):      # (a longer list is refused by the library, by its length)
+                    dst[j][0], dst[j][1] = int(p_), int(e)
+        first = np.zeros(max(1, len(domains)), dtype=np.uint64)
+        count = np.zeros(max(1, len(domains)), dtype=np.uint32)
+        check(self.lib.ss_check_constraints(self.handle, C.byref(prog), _ptr_array(cols), len(cols), log_n, doms, len(domains),
+                                            first.ctypes.data_as(C.POINTER(C.c_uint64)), count.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return first[:len(domains)], count[:len(domains)]
+
     def zero(self, buf, nbytes=None):
         check(self.lib.ss_dev_zero(self.handle, _ptr_of(buf), buf.nbytes if nbytes is None else nbytes))
 

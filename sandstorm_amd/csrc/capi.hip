@@ -2678,6 +2678,97 @@ ss_status ss_eval_quotient_rows(ss_ctx *ctx, const ss_air_program *prog, const u
     return eval_quotient_impl(ctx, prog, d_col_blocks, ncols, log_n, log_blowup, offset, row0, nrows, block_rows, d_out);
 }
 
+// The trace against its constraints one by one (quotient.hip: the checking instantiation of the interpreter).  Always interpreted:
+// the compiled kernels are the composition's.
+ss_status ss_check_constraints(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n,
+                               const ss_check_domain *domains, uint32_t n_checks, uint64_t *first_row_out, uint32_t *count_out) {
+    static_assert(VM_CHECK_MAX_FACTORS == SS_CHECK_MAX_FACTORS, "kernels.h and the header disagree");
+    if (!ctx || !prog || !d_cols || !domains || !first_row_out || !count_out) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!prog->code || prog->n_instr == 0 || n_checks == 0) return fail(SS_ERR_INVALID, "empty program");
+    if (!valid_log(log_n) || log_n > 31) return fail(SS_ERR_INVALID, "size out of range");
+    if (ncols > (uint32_t)MAX_COLS) return fail(SS_ERR_UNSUPPORTED, "ncols %u > %d", ncols, MAX_COLS);
+    if (has_null((const void *const *)d_cols, ncols)) return fail(SS_ERR_INVALID, "NULL column");
+    const uint64_t n = 1ull << log_n;
+    std::vector<uint8_t> seen(n_checks, 0);
+    for (uint32_t pc = 0; pc < prog->n_instr; ++pc) {
+        const uint32_t w0 = prog->code[2 * pc], w1 = prog->code[2 * pc + 1];
+        const uint32_t op = w0 & 0xff, d = (w0 >> 8) & 0xf, kind = (w0 >> 12) & 0xf;
+        if (op == SS_OP_OUT) return fail(SS_ERR_INVALID, "instruction %u: OUT in a check program", pc);
+        if ((op > SS_OP_ST && op != SS_OP_CHECK) || d > 3) return fail(SS_ERR_INVALID, "instruction %u: bad opcode/accumulator", pc);
+        if (op == SS_OP_CHECK) {
+            if (w1 >= n_checks) return fail(SS_ERR_INVALID, "instruction %u: check %u out of range", pc, w1);
+            if (seen[w1]++) return fail(SS_ERR_INVALID, "instruction %u: check %u appears twice", pc, w1);
+        }
+        if (op == SS_OP_ST && w1 >= prog->n_slots) return fail(SS_ERR_INVALID, "instruction %u: slot %u out of range", pc, w1);
+        if (op <= SS_OP_MUL) {
+            if (kind > SS_SRC_X) return fail(SS_ERR_INVALID, "instruction %u: bad operand kind", pc);
+            if (kind == SS_SRC_ACC && w1 > 3) return fail(SS_ERR_INVALID, "instruction %u: bad accumulator", pc);
+            if (kind == SS_SRC_SLOT && w1 >= prog->n_slots) return fail(SS_ERR_INVALID, "instruction %u: slot %u out of range", pc, w1);
+            if (kind == SS_SRC_CONST && w1 >= prog->n_consts) return fail(SS_ERR_INVALID, "instruction %u: constant %u out of range", pc, w1);
+            if (kind == SS_SRC_TRACE && (w1 >> 24) >= ncols) return fail(SS_ERR_INVALID, "instruction %u: column %u out of range", pc, w1 >> 24);
+            if (kind == SS_SRC_TABLE && (w1 >= prog->n_tables || !prog->d_tables || !prog->table_desc))
+                return fail(SS_ERR_INVALID, "instruction %u: table %u out of range", pc, w1);
+        }
+    }
+    for (uint32_t k = 0; k < n_checks; ++k)
+        if (!seen[k]) return fail(SS_ERR_INVALID, "check %u does not appear in the program", k);
+    std::vector<VmCheckDomain> doms(n_checks);
+    for (uint32_t k = 0; k < n_checks; ++k) {
+        const ss_check_domain &src = domains[k];
+        if (src.n_num > SS_CHECK_MAX_FACTORS || src.n_den > SS_CHECK_MAX_FACTORS)
+            return fail(SS_ERR_UNSUPPORTED, "check %u: a domain of %u numerator and %u denominator factors exceeds SS_CHECK_MAX_FACTORS = %u", k, src.n_num,
+                        src.n_den, SS_CHECK_MAX_FACTORS);
+        VmCheckDomain &dst = doms[k];
+        memset(&dst, 0, sizeof(dst));
+        dst.n_num = src.n_num; dst.n_den = src.n_den;
+        for (uint32_t j = 0; j < src.n_num; ++j) { dst.num[j][0] = (uint32_t)(src.num[j][0] & (n - 1)); dst.num[j][1] = (uint32_t)(src.num[j][1] & (n - 1)); }
+        for (uint32_t j = 0; j < src.n_den; ++j) { dst.den[j][0] = (uint32_t)(src.den[j][0] & (n - 1)); dst.den[j][1] = (uint32_t)(src.den[j][1] & (n - 1)); }
+    }
+    uint64_t lanes = 256ull * 256 * 4;
+    if (lanes > n) lanes = n < 256 ? 256 : n;
+    const size_t code_b = ((size_t)prog->n_instr + 1) * 32, const_b = (size_t)(prog->n_consts ? prog->n_consts : 1) * 32;
+    const size_t slots_b = (size_t)(prog->n_slots ? prog->n_slots : 1) * lanes * 32;
+    const size_t dom_b = (sizeof(VmCheckDomain) * n_checks + 31) / 32 * 32, first_b = ((size_t)n_checks * 8 + 31) / 32 * 32, count_b = ((size_t)n_checks * 4 + 31) / 32 * 32;
+    ss_status st = ctx->ensure_scratch(slots_b + 2 * const_b + code_b + dom_b + first_b + count_b + 256);
+    if (st != SS_OK) return st;
+    char *p = (char *)ctx->scratch;
+    Fp *d_slots = (Fp *)p; p += slots_b;
+    Fp *d_consts = (Fp *)p; p += const_b;
+    Fp *d_consts_r280 = (Fp *)p; p += const_b;
+    uint32_t *d_code = (uint32_t *)p; p += code_b;
+    VmCheckDomain *d_doms = (VmCheckDomain *)p; p += dom_b;
+    uint64_t *d_first = (uint64_t *)p; p += first_b;
+    uint32_t *d_count = (uint32_t *)p;
+    hipStream_t s = ctx->stream;
+    VmResolve rs;
+    for (int c = 0; c < MAX_COLS; ++c) rs.cols[c] = c < (int)ncols ? (const void *)d_cols[c] : nullptr;
+    rs.consts = d_consts; rs.consts_r280 = d_consts_r280; rs.tables = prog->d_tables; rs.slots = d_slots; rs.table_desc = prog->table_desc;
+    rs.lanes = lanes; rs.log_blowup = 0; rs.trace_mask = (uint32_t)(n - 1); rs.row0 = 0;
+    std::vector<uint32_t> dev_code(((size_t)prog->n_instr + 1) * 8);
+    quotient_build_device_code(prog->code, prog->n_instr, rs, dev_code.data());
+    HIP_TRY(hipMemcpyAsync(d_code, dev_code.data(), code_b, hipMemcpyHostToDevice, s));
+    std::vector<Fp> consts_r280(prog->n_consts);
+    if (prog->n_consts) {
+        HIP_TRY(hipMemcpyAsync(d_consts, prog->consts, (size_t)prog->n_consts * 32, hipMemcpyHostToDevice, s));
+        Fp two24 = fp_zero(); two24.v[0] = 1u << 24;
+        const Fp f = fp_to_mont(two24);
+        for (uint32_t k = 0; k < prog->n_consts; ++k) consts_r280[k] = fp_mul(fp_from_limbs64(prog->consts + 4 * (size_t)k), f);
+        HIP_TRY(hipMemcpyAsync(d_consts_r280, consts_r280.data(), (size_t)prog->n_consts * 32, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(d_doms, doms.data(), sizeof(VmCheckDomain) * n_checks, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_first, 0xff, (size_t)n_checks * 8, s));
+    HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)n_checks * 4, s));
+    const Fp w = root_of_unity(log_n);
+    {
+        ss_ctx::Scope prof(ctx, SS_PROF_QUOTIENT);
+        HIP_TRY(launch_quotient_vm_check(s, d_code, prog->n_instr + 1, d_slots, lanes, w, fp_pow_u64(w, lanes), n, d_doms, d_first, d_count));
+    }
+    HIP_TRY(hipMemcpyAsync(first_row_out, d_first, (size_t)n_checks * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(count_out, d_count, (size_t)n_checks * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SS_OK;
+}
+
 
 // ------------------------------------------------------------------- the 64-bit field variant (X4)
 }  // extern "C"

@@ -315,4 +315,13 @@ void quotient_build_device_code(const uint32_t *code, uint32_t n_instr, const Vm
 hipError_t launch_quotient_vm(hipStream_t st, const uint32_t *d_code, uint32_t n_entries, Fp *d_slots, uint64_t lanes,
                               const Fp &offset, const Fp &w, const Fp &wstep, uint64_t npoints, uint32_t xcd_split, Fp *out);
 
+// a constraint's domain as the checking interpreter reads it (ss_check_domain with 32-bit factors: p <= n, e < n <= 2^31)
+static constexpr uint32_t VM_CHECK_MAX_FACTORS = 16;      // = SS_CHECK_MAX_FACTORS
+struct VmCheckDomain {
+    uint32_t n_num, n_den;
+    uint32_t num[VM_CHECK_MAX_FACTORS][2], den[VM_CHECK_MAX_FACTORS][2];
+};
+hipError_t launch_quotient_vm_check(hipStream_t st, const uint32_t *d_code, uint32_t n_entries, Fp *d_slots, uint64_t lanes, const Fp &w,
+                                    const Fp &wstep, uint64_t npoints, const VmCheckDomain *d_domains, uint64_t *d_first_row, uint32_t *d_count);
+
 }  // namespace ss

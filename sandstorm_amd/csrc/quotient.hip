@@ -69,6 +69,7 @@ struct VmArgs {
 static constexpr uint32_t VM_MAX_BOUND = 8;       // 8 * 2p * 2p / 2^256 + p < 2p: products stay < 2^252
 static constexpr uint32_t VM_OP_NOP = 8;
 static constexpr uint32_t VM_OP_MULR = 9;         // MUL by a constant kept in R280 form (fl252.h): the cheaper fl_mul_r280
+static_assert(SS_OP_CHECK > VM_OP_MULR && SS_OP_CHECK < 16, "the public CHECK opcode shares the 4-bit field with the internal ones");
 static constexpr uint32_t VM_F_RV = 1u << 10, VM_F_RS = 1u << 11, VM_F_P = 1u << 12, VM_F_PL = 1u << 13;
 
 // One instruction on a NAMED accumulator: the destination index is wave-uniform, so the caller
@@ -101,7 +102,44 @@ __device__ __forceinline__ Fp vm_load(const vm_global_u32x4 *p) {
     return r;
 }
 
-__global__ __launch_bounds__(256, 4) void quotient_vm_kernel(VmArgs a) {
+// ---- the checking instantiation (ss_check_constraints): the program has one CHECK k per constraint instead of one OUT, the domain is
+// the trace domain itself (x = g^row) and nothing is written but, per violated constraint, its first row and its number of rows.
+// Whether row r belongs to domain k is integer arithmetic on the wave-uniform descriptor: the factor X^p - g^e vanishes at g^r iff
+// p r = e (mod n); the row is in the domain iff some denominator factor vanishes there and no numerator factor does.
+struct VmCheckArgs {
+    const VmCheckDomain *domains;       // [n_checks]
+    unsigned long long *first_row;      // [n_checks], preset to ~0
+    uint32_t *count;                    // [n_checks], preset to 0
+};
+__device__ __forceinline__ bool vm_row_in_domain(const VmCheckDomain &d, uint32_t row, uint32_t nmask) {
+    bool num = false, den = false;
+    for (uint32_t j = 0; j < d.n_num; ++j) num |= (((uint64_t)d.num[j][0] * row - d.num[j][1]) & nmask) == 0;
+    for (uint32_t j = 0; j < d.n_den; ++j) den |= (((uint64_t)d.den[j][0] * row - d.den[j][1]) & nmask) == 0;
+    return den && !num;
+}
+// One CHECK: a wave reduces (smallest violating row, violating lanes) with 12 shuffles and its first lane issues at most one atomic
+// pair - none on a clean trace, n / 64 per constraint on a wholly wrong one.  Every lane of the wave gets here (the point loop below
+// has a workgroup-uniform trip count in this instantiation); one whose point lies outside the domain takes part as "no violation".
+__device__ __forceinline__ void vm_check(const VmCheckArgs &c, uint32_t k, const Fl &v, bool live, uint32_t row, uint32_t nmask) {
+    const Fp r = fl_to_fp(v);
+    bool bad = live && (r.v[0] | r.v[1] | r.v[2] | r.v[3] | r.v[4] | r.v[5] | r.v[6] | r.v[7]) != 0;
+    if (bad) bad = vm_row_in_domain(c.domains[k], row, nmask);
+    uint32_t first = bad ? row : 0xffffffffu;
+    int cnt = bad ? 1 : 0;
+    for (int m = 32; m; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)first, m, 64);
+        first = o < first ? o : first;
+        cnt += __shfl_xor(cnt, m, 64);
+    }
+    if ((threadIdx.x & 63u) == 0 && cnt) {
+        atomicMin(c.first_row + k, (unsigned long long)first);
+        atomicAdd(c.count + k, (uint32_t)cnt);
+    }
+}
+
+// the interpreter's body: CHECK = false is ss_eval_quotient's kernel, CHECK = true ss_check_constraints'
+template <bool CHECK>
+__device__ __forceinline__ void quotient_vm_body(const VmArgs &a, const VmCheckArgs &chk) {
     const uint64_t N = a.npoints;
     const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t lane = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;       // slot-file index
@@ -118,6 +156,8 @@ __global__ __launch_bounds__(256, 4) void quotient_vm_kernel(VmArgs a) {
     } else {
         i0 = lane; stride = lanes; count = (N + lanes - 1 - lane) / lanes;
     }
+    // checking: every lane of a workgroup makes as many sweeps as its first lane (they differ only where N < 256)
+    if (CHECK) count = (N + lanes - 1 - (lane - threadIdx.x)) / lanes;
     Fl x = fl_from_fp(fp_mul(a.offset, fp_pow_u64(a.w, i0)));
     const Fl wstep = fl_from_fp(a.wstep);                                          // w^stride
     // the program is read-only for the kernel's lifetime: constant address space => scalar loads
@@ -161,10 +201,22 @@ __global__ __launch_bounds__(256, 4) void quotient_vm_kernel(VmArgs a) {
             default: vm_exec(w0, acc3, src, a, w1, lanes, lane, i); break;
             }
             if ((w0 & VM_F_P) && op == SS_OP_ST) pre = vm_load(nptr);
+            if (CHECK && op == SS_OP_CHECK) {
+                const uint32_t nmask = (uint32_t)N - 1u;
+                switch ((w0 >> 4) & 3u) {
+                case 0: vm_check(chk, w1, acc0, i < N, i32, nmask); break;
+                case 1: vm_check(chk, w1, acc1, i < N, i32, nmask); break;
+                case 2: vm_check(chk, w1, acc2, i < N, i32, nmask); break;
+                default: vm_check(chk, w1, acc3, i < N, i32, nmask); break;
+                }
+            }
         }
         x = fl_mul(x, wstep);
     }
 }
+
+__global__ __launch_bounds__(256, 4) void quotient_vm_kernel(VmArgs a) { quotient_vm_body<false>(a, VmCheckArgs{nullptr, nullptr, nullptr}); }
+__global__ __launch_bounds__(256, 4) void quotient_vm_check_kernel(VmArgs a, VmCheckArgs c) { quotient_vm_body<true>(a, c); }
 
 // Caller's 2-word program -> resolved device program (n_instr + 1 entries of 8 words, see above).
 void quotient_build_device_code(const uint32_t *code, uint32_t n_instr, const VmResolve &r, uint32_t *dev) {
@@ -243,6 +295,18 @@ hipError_t launch_quotient_vm(hipStream_t st, const uint32_t *d_code, uint32_t n
     a.code = d_code; a.slots = d_slots; a.out = out; a.offset = offset; a.w = w; a.wstep = wstep;
     a.n_entries = n_entries; a.npoints = npoints; a.xcd_split = xcd_split;
     hipLaunchKernelGGL(quotient_vm_kernel, dim3((uint32_t)(lanes / 256)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// the trace domain (npoints = n, a power of two, x_i = w^i), `lanes` a multiple of 256; the three arrays hold n_checks entries
+hipError_t launch_quotient_vm_check(hipStream_t st, const uint32_t *d_code, uint32_t n_entries, Fp *d_slots, uint64_t lanes, const Fp &w,
+                                    const Fp &wstep, uint64_t npoints, const VmCheckDomain *d_domains, uint64_t *d_first_row, uint32_t *d_count) {
+    VmArgs a;
+    a.code = d_code; a.slots = d_slots; a.out = nullptr; a.offset = fp_one(); a.w = w; a.wstep = wstep;
+    a.n_entries = n_entries; a.npoints = npoints; a.xcd_split = 0;
+    VmCheckArgs c;
+    c.domains = d_domains; c.first_row = (unsigned long long *)d_first_row; c.count = d_count;
+    hipLaunchKernelGGL(quotient_vm_check_kernel, dim3((uint32_t)(lanes / 256)), dim3(256), 0, st, a, c);
     return hipGetLastError();
 }
 

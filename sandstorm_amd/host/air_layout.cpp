@@ -167,6 +167,39 @@ Felt LayoutAir::composition_at(uint64_t n, const std::vector<Felt> &ch, const Fe
     return evaluate(g, root, z, [&](uint32_t c, uint32_t o) { return cell.at({c, o}); }, [&](uint32_t t) { return table_value_at(specs_.at(t), z); });
 }
 
+LayoutAir::CheckProgramData LayoutAir::build_check_program(uint64_t n, const std::vector<Felt> &ch) {
+    if (n != n_) throw std::runtime_error("this " + name + " AIR was built for another trace length");
+    CheckProgramData out;
+    Graph g;
+    collect_ = &out.checks;
+    try { composition(g, ch, felt_from_u64(1)); } catch (...) { collect_ = nullptr; throw; }
+    collect_ = nullptr;
+    std::vector<int> roots;
+    for (auto &c : out.checks) roots.push_back(c.numerator);
+    for (auto &nd : g.nodes())
+        if (nd.kind == NodeKind::Table && nd.p0 >= num_periodic_columns()) throw std::runtime_error("a constraint's numerator reads a table that is no periodic column");
+    out.program = lower_checks(g, roots);
+    if (check_desc_.empty() && num_periodic_columns()) {
+        std::vector<Felt> host;
+        for (size_t c = 0; c < num_periodic_columns(); ++c) {
+            const std::vector<Felt> v = column_values(c);
+            const uint64_t period = column_period(c), step = period / v.size();
+            uint32_t ll = 0;
+            while ((1ull << ll) < period) ++ll;
+            check_desc_.push_back((uint32_t)host.size()); check_desc_.push_back(ll);
+            for (uint64_t r = 0; r < period; ++r) host.push_back(v[r / step]);
+        }
+        if (ctx_) {
+            check_tables_.reset(new DeviceBuffer(ctx_, 32 * host.size()));
+            ok(ss_upload(ctx_, check_tables_->u64(), host.data(), host.size() * 32));
+            ok(ss_ctx_sync(ctx_));
+        }
+    }
+    out.table_desc = check_desc_;
+    out.d_tables = check_tables_ ? check_tables_->u64() : nullptr;
+    return out;
+}
+
 std::vector<uint64_t> LayoutAir::describe_tables() const {
     std::vector<uint64_t> out{specs_.size()};
     for (auto &s : specs_) {
@@ -210,6 +243,7 @@ E LayoutAir::multiplier(Graph &g, const Domain &d) {
 }
 
 void LayoutAir::Composer::add(const std::string &domain_name, const Domain &d, const E &numerator) {
+    if (air_.collect_) { air_.collect_->push_back(Check{domain_name, d, numerator.id}); return; }
     const E term = numerator * E{&g_, g_.runtime_constant(Graph::sym("alpha^", count_++), apow_)};
     auto it = std::find_if(groups_.begin(), groups_.end(), [&](const Group &p) { return p.name == domain_name; });
     if (it == groups_.end()) groups_.push_back(Group{domain_name, d, term.id});
@@ -218,6 +252,7 @@ void LayoutAir::Composer::add(const std::string &domain_name, const Domain &d, c
 }
 
 int LayoutAir::Composer::total() {
+    if (air_.collect_) return air_.collect_->empty() ? -1 : air_.collect_->back().numerator;
     int total = -1;
     for (auto &gr : groups_) {
         const E term = E{&g_, gr.sum} * air_.multiplier(g_, gr.d);
@@ -310,6 +345,94 @@ void LayoutAir::build_tables() {
 }
 
 }  // namespace layout
+
+// ---- the trace against the AIR, constraint by constraint
+namespace {
+#include "constraint_names.inc"
+// (constraint name, domain name) of constraint k of a layout; an AIR the table does not know gets the C++ domain's name alone
+std::pair<std::string, std::string> constraint_name(const std::string &layout, size_t k, size_t total, const std::string &fallback_domain) {
+    const char *const (*tab)[2] = nullptr;
+    size_t len = 0;
+    if (layout == "recursive") { tab = CONSTRAINT_NAMES_RECURSIVE; len = sizeof(CONSTRAINT_NAMES_RECURSIVE) / sizeof(CONSTRAINT_NAMES_RECURSIVE[0]); }
+    if (layout == "starknet") { tab = CONSTRAINT_NAMES_STARKNET; len = sizeof(CONSTRAINT_NAMES_STARKNET) / sizeof(CONSTRAINT_NAMES_STARKNET[0]); }
+    if (tab && len != total) throw std::runtime_error("constraint_names.inc is stale: the " + layout + " AIR has " + std::to_string(total) + " constraints, the table " + std::to_string(len));
+    if (!tab) return {"constraint " + std::to_string(k), fallback_domain};
+    return {tab[k][0], tab[k][1]};
+}
+}  // namespace
+
+std::vector<ss_check_domain> check_domains(const layout::LayoutAir::CheckProgramData &cp) {
+    std::vector<ss_check_domain> doms(cp.checks.size());
+    for (size_t k = 0; k < doms.size(); ++k) {
+        const layout::Domain &d = cp.checks[k].domain;
+        if (d.num.size() > SS_CHECK_MAX_FACTORS || d.den.size() > SS_CHECK_MAX_FACTORS)
+            throw std::runtime_error("domain " + cp.checks[k].domain_name + " has more than SS_CHECK_MAX_FACTORS factors");
+        memset(&doms[k], 0, sizeof(doms[k]));
+        doms[k].n_num = (uint32_t)d.num.size(); doms[k].n_den = (uint32_t)d.den.size();
+        for (size_t j = 0; j < d.num.size(); ++j) { doms[k].num[j][0] = d.num[j].p; doms[k].num[j][1] = d.num[j].e; }
+        for (size_t j = 0; j < d.den.size(); ++j) { doms[k].den[j][0] = d.den[j].p; doms[k].den[j][1] = d.den[j].e; }
+    }
+    return doms;
+}
+
+std::vector<ConstraintFailure> check_trace(ss_ctx *ctx, Air &air, const std::vector<const uint64_t *> &cols, uint32_t log_n, const std::vector<Felt> &challenges) {
+    layout::LayoutAir *la = dynamic_cast<layout::LayoutAir *>(&air);
+    if (!la) throw std::runtime_error("the trace check covers the recursive and starknet layouts; the " + air.name + " AIR has no check program");
+    if (!ctx) throw std::runtime_error("the trace check needs a device context");
+    if (cols.size() != air.num_base_columns + air.num_extension_columns) throw std::runtime_error("the trace check takes the base and the extension columns");
+    if (challenges.size() != air.num_challenges) throw std::runtime_error("the trace check takes the AIR's " + std::to_string(air.num_challenges) + " challenges");
+    const layout::LayoutAir::CheckProgramData cp = la->build_check_program(1ull << log_n, challenges);
+    const std::vector<ss_check_domain> doms = check_domains(cp);
+    std::vector<uint64_t> consts(4 * cp.program.consts.size());
+    for (size_t i = 0; i < cp.program.consts.size(); ++i) memcpy(consts.data() + 4 * i, cp.program.consts[i].data(), 32);
+    ss_air_program prog;
+    prog.code = cp.program.code.data(); prog.n_instr = cp.program.n_instr();
+    prog.consts = consts.data(); prog.n_consts = (uint32_t)cp.program.consts.size();
+    prog.d_tables = cp.d_tables; prog.table_desc = cp.table_desc.data(); prog.n_tables = (uint32_t)(cp.table_desc.size() / 2);
+    prog.n_slots = cp.program.n_slots;
+    std::vector<uint64_t> first(doms.size());
+    std::vector<uint32_t> count(doms.size());
+    layout::ok(ss_check_constraints(ctx, &prog, cols.data(), (uint32_t)cols.size(), log_n, doms.data(), (uint32_t)doms.size(), first.data(), count.data()));
+    std::vector<ConstraintFailure> out;
+    for (size_t k = 0; k < doms.size(); ++k) {
+        if (first[k] == UINT64_MAX) continue;
+        const auto nm = constraint_name(air.name, k, doms.size(), cp.checks[k].domain_name);
+        out.push_back(ConstraintFailure{(uint32_t)k, nm.first, nm.second, first[k], count[k]});
+    }
+    return out;
+}
+
+std::string describe_failures(const std::vector<ConstraintFailure> &f) {
+    if (f.empty()) return "the trace satisfies the AIR";
+    const ConstraintFailure &a = f.front();
+    return "trace does not satisfy the AIR: " + std::to_string(f.size()) + (f.size() == 1 ? " constraint fails" : " constraints fail") + "; first: #" +
+           std::to_string(a.index) + " " + a.name + " (" + a.domain + ") at row " + std::to_string(a.first_row) + ", " + std::to_string(a.count) +
+           (a.count == 1 ? " row" : " rows");
+}
+
+// the check program of a layout AIR (host-side checks; works without a context): n_instr, code words..., n_consts, 4 limbs each...,
+// n_slots, n_tables, (offset, log2 length) per table, n_checks, then per check: #num, (p, e)..., #den, (p, e)...
+std::vector<uint64_t> layout_air_check_program(Air &air, uint64_t n, const std::vector<Felt> &challenges) {
+    layout::LayoutAir *la = dynamic_cast<layout::LayoutAir *>(&air);
+    if (!la) throw std::runtime_error("not a layout AIR");
+    const layout::LayoutAir::CheckProgramData cp = la->build_check_program(n, challenges);
+    check_domains(cp);                                   // (refuses a domain the kernel's descriptor cannot hold)
+    std::vector<uint64_t> out{cp.program.n_instr()};
+    for (uint32_t w : cp.program.code) out.push_back(w);
+    out.push_back(cp.program.consts.size());
+    for (auto &c : cp.program.consts) for (int k = 0; k < 4; ++k) out.push_back(c[k]);
+    out.push_back(cp.program.n_slots);
+    out.push_back(cp.table_desc.size() / 2);
+    for (uint32_t v : cp.table_desc) out.push_back(v);
+    out.push_back(cp.checks.size());
+    for (auto &c : cp.checks) {
+        out.push_back(c.domain.num.size());
+        for (auto &f : c.domain.num) { out.push_back(f.p); out.push_back(f.e); }
+        out.push_back(c.domain.den.size());
+        for (auto &f : c.domain.den) { out.push_back(f.p); out.push_back(f.e); }
+    }
+    return out;
+}
 
 std::vector<uint64_t> layout_air_tables(const Air &air) {
     const layout::LayoutAir *r = dynamic_cast<const layout::LayoutAir *>(&air);

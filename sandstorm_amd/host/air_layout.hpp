@@ -72,6 +72,13 @@ public:
     Felt composition_at(uint64_t n, const std::vector<Felt> &ch, const Felt &alpha, const Felt &z, const std::vector<Felt> &ood) override;
     // flat description of the tables for host-side checks: per table kind, e, #num, (p, e)..., #den, (p, e)...
     std::vector<uint64_t> describe_tables() const;
+    // The constraints one by one, for the trace check (ssh::check_trace): a program with one CHECK per constraint in the reference's
+    // order, each over the constraint's bare numerator - no power of the composition coefficient, no multiplier - and the domain
+    // it is enforced on.  Its tables are the periodic columns alone, over the TRACE domain (a column's values along one period,
+    // each held for as many rows as its step), built on first use; d_tables is NULL for an AIR without a context.
+    struct Check { std::string domain_name; Domain domain; int numerator; };
+    struct CheckProgramData { Program program; std::vector<Check> checks; const uint64_t *d_tables = nullptr; std::vector<uint32_t> table_desc; };
+    CheckProgramData build_check_program(uint64_t n, const std::vector<Felt> &ch);
 
 private:
     // the program lowered for `ch` with a placeholder composition coefficient, and where its powers sit among the constants
@@ -102,6 +109,7 @@ protected:
     class Composer {
     public:
         Composer(LayoutAir &air, Graph &g, const Felt &alpha) : air_(air), g_(g), alpha_(alpha), apow_(felt_from_u64(1)) {}
+        // (while the AIR collects its checks - build_check_program - add() only records the constraint and total() is its last numerator)
         void add(const std::string &domain_name, const Domain &d, const E &numerator);
         int total();
     private:
@@ -126,6 +134,9 @@ protected:
     std::vector<uint32_t> desc_;
     std::unique_ptr<DeviceBuffer> tables_;
     mutable std::map<size_t, std::vector<Felt>> column_coeffs_;
+    std::vector<Check> *collect_ = nullptr;          // set while build_check_program runs composition()
+    std::unique_ptr<DeviceBuffer> check_tables_;
+    std::vector<uint32_t> check_desc_;
 };
 
 // compute_public_memory_quotient (layouts/src/utils.rs:14-46) and compute_diluted_cumulative_value (utils.rs:48-108)

@@ -144,6 +144,28 @@ Program lower(const Graph &g, int root) {
     return L.prog;
 }
 
+// One program for many roots: reference counts over everything reachable from any of them (a root counts as one more use of its
+// node), so a sub-expression that two constraints share - or a root that is one of a later root's sub-expressions, or the same
+// root twice - is computed once and parked in a slot until its last reader, across the CHECKs.
+Program lower_checks(const Graph &g, const std::vector<int> &roots) {
+    Lowerer L(g);
+    std::vector<char> seen(g.nodes().size(), 0);
+    std::vector<int> stack(roots.begin(), roots.end());
+    while (!stack.empty()) {
+        int n = stack.back(); stack.pop_back();
+        if (seen[n]) continue;
+        seen[n] = 1;
+        const Node &nd = g.nodes()[n];
+        for (int c : {nd.a, nd.b}) if (c >= 0) { ++L.uses[c]; stack.push_back(c); }
+    }
+    for (int r : roots) ++L.uses[r];
+    for (size_t k = 0; k < roots.size(); ++k) {
+        L.gen(roots[k], 0);
+        L.emit(SS_OP_CHECK, 0, 0, (uint32_t)k);
+    }
+    return L.prog;
+}
+
 Felt evaluate(const Graph &g, int root, const Felt &x, const std::function<Felt(uint32_t, uint32_t)> &trace_at,
               const std::function<Felt(uint32_t)> &table_at) {
     const auto &nodes = g.nodes();

@@ -72,6 +72,10 @@ struct Program {
 // code leaving `root` in accumulator 0 followed by OUT
 Program lower(const Graph &g, int root);
 
+// code leaving roots[k] in accumulator 0 followed by CHECK k, for every k in order (ss_check_constraints); sub-expressions shared
+// between roots are computed once
+Program lower_checks(const Graph &g, const std::vector<int> &roots);
+
 // Direct evaluation of the DAG at one point (the definition the lowered program must reproduce; the verifier's side of
 // the out-of-domain identity).  trace_at(col, row offset) and table_at(index) supply the leaves.
 Felt evaluate(const Graph &g, int root, const Felt &x, const std::function<Felt(uint32_t, uint32_t)> &trace_at,

@@ -180,6 +180,7 @@ static int prove_sharded_impl(ss_ctx *ctx, ssh_air *air_h, int tree_kind, uint32
     try {
         if (!ctx || !air_h || !seed || (!group && !rccl)) throw std::runtime_error("ssh_prove_sharded: NULL argument");
         Air *air = reinterpret_cast<Air *>(air_h);
+        refuse_validation(*air);
         Claim claim;
         claim.air = air; claim.tree_kind = tree_kind; claim.n_friendly_layers = n_friendly_layers; claim.coin_kind = coin_kind;
         ProofOptions opt;
@@ -739,6 +740,7 @@ int ssh_prove_files_sharded_device(ss_ctx *ctx, int layout, const uint8_t *trace
     try {
         if (proof_bytes && proof_len) { *proof_bytes = nullptr; *proof_len = 0; }
         if (!ctx || !air_h || !seed || (!group && !rccl)) throw std::runtime_error("ssh_prove_files_sharded_device: NULL argument");
+        refuse_validation(*reinterpret_cast<Air *>(air_h));
         const auto t_start = std::chrono::steady_clock::now();
         if (rank >= world) throw std::runtime_error("ssh_prove_files_sharded_device: rank " + std::to_string(rank) + " of " + std::to_string(world));
         std::unique_ptr<Transport> local = lg ? make_local_transport(*lg, rank) : nullptr;
@@ -946,6 +948,11 @@ int ssh_gl_prove_files_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t tr
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }
 
+static std::vector<Felt> felts_of_challenges(const uint64_t *challenges, uint32_t nchallenges) {
+    std::vector<Felt> ch(nchallenges);
+    for (uint32_t i = 0; i < nchallenges; ++i) memcpy(ch[i].data(), challenges + 4 * i, 32);
+    return ch;
+}
 // the lowered composition program for these challenges and its table descriptions, as one u64 blob:
 // n_instr, code words..., n_consts, 4 limbs each..., n_slots, then layout_air_tables()
 int ssh_air_dump(ssh_air *air_h, uint64_t n, const uint64_t *challenges, uint32_t nchallenges, const uint64_t alpha[4], uint64_t **blob, uint64_t *blob_len) {
@@ -994,6 +1001,54 @@ int ssh_air_program(ssh_air *air_h, uint64_t n, const uint64_t *challenges, uint
         *blob = (uint64_t *)malloc(out.size() * 8);
         memcpy(*blob, out.data(), out.size() * 8);
         *blob_len = out.size();
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// The check program of a layout AIR (Air handle created with or without a context) as one u64 blob: n_instr, code words..., n_consts,
+// 4 limbs each..., n_slots, n_tables, (offset, log2 length) per table, n_checks, then per check #num, (p, e)..., #den, (p, e)...
+int ssh_air_check_program(ssh_air *air_h, uint64_t n, const uint64_t *challenges, uint32_t nchallenges, uint64_t **blob, uint64_t *blob_len) {
+    try {
+        Air *air = reinterpret_cast<Air *>(air_h);
+        const std::vector<uint64_t> out = layout_air_check_program(*air, n, felts_of_challenges(challenges, nchallenges));
+        *blob = (uint64_t *)malloc(out.size() * 8);
+        memcpy(*blob, out.data(), out.size() * 8);
+        *blob_len = out.size();
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// Air::validate_trace: the provers that end in Prover::prove (ssh_prove, ssh_prove_wire, ssh_prove_files, ssh_prove_files_device) check
+// the trace against every constraint before they commit to the extension trace and fail with the first violated constraint's name and
+// row; the sharded entry points refuse an AIR that has it on.  Off when an AIR is created.
+int ssh_air_set_validation(ssh_air *air_h, int on) {
+    if (!air_h) { g_err = "ssh_air_set_validation: NULL argument"; return 1; }
+    reinterpret_cast<Air *>(air_h)->validate_trace = on != 0;
+    return 0;
+}
+// The trace against the AIR with the caller's challenges (ssh::check_trace): d_cols = the ncols = base + extension columns on the
+// trace domain.  Room for `capacity` failures in the output arrays (indices, first rows, counts); *n_failures = how many constraints
+// fail (it may exceed capacity).  *report (optional; ssh_free) = one line per failing constraint: "index\tname\tdomain\tfirst row\tcount".
+int ssh_check_trace(ss_ctx *ctx, ssh_air *air_h, const uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n, const uint64_t *challenges,
+                    uint32_t nchallenges, uint32_t capacity, uint32_t *indices_out, uint64_t *first_rows_out, uint32_t *counts_out, uint32_t *n_failures,
+                    char **report) {
+    try {
+        if (!ctx || !air_h || !d_cols || !n_failures) throw std::runtime_error("ssh_check_trace: NULL argument");
+        Air *air = reinterpret_cast<Air *>(air_h);
+        const std::vector<ConstraintFailure> bad = check_trace(ctx, *air, std::vector<const uint64_t *>(d_cols, d_cols + ncols), log_n,
+                                                               felts_of_challenges(challenges, nchallenges));
+        *n_failures = (uint32_t)bad.size();
+        std::string text;
+        for (size_t k = 0; k < bad.size(); ++k) {
+            if (k < capacity) {
+                if (indices_out) indices_out[k] = bad[k].index;
+                if (first_rows_out) first_rows_out[k] = bad[k].first_row;
+                if (counts_out) counts_out[k] = bad[k].count;
+            }
+            text += std::to_string(bad[k].index) + "\t" + bad[k].name + "\t" + bad[k].domain + "\t" + std::to_string(bad[k].first_row) + "\t" + std::to_string(bad[k].count) + "\n";
+        }
+        if (report) {
+            *report = (char *)malloc(text.size() + 1);
+            memcpy(*report, text.c_str(), text.size() + 1);
+        }
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }

@@ -277,6 +277,13 @@ Proof Prover::prove(const Digest &coin_seed, const Matrix &base_trace, const Ext
     std::unique_ptr<MerkleTree> ext_tree;
     if (air.num_extension_columns) {
         Matrix ext = build_extension(proof.challenges);
+        if (air.validate_trace) {            // the caller's base columns and the fresh extension columns, with this proof's challenges
+            std::vector<const uint64_t *> all(base_trace.cols.begin(), base_trace.cols.end());
+            all.insert(all.end(), ext.cols.begin(), ext.cols.end());
+            const std::vector<ConstraintFailure> bad = check_trace(ctx_, air, all, log_n, proof.challenges);
+            if (!bad.empty()) throw std::runtime_error(describe_failures(bad));
+            mark("trace check");
+        }
         ext_lde = Matrix::alloc(ctx_, ext.num_cols(), N);
         ext_co = Matrix::alloc(ctx_, ext.num_cols(), n);
         ok(ss_lde_fp252(ctx_, (const uint64_t *const *)ext.cols.data(), ext.num_cols(), log_n, lb, g.data(), ext_lde.cols.data(),

@@ -125,6 +125,10 @@ public:
     // (ce_blowup_factor, src/lib.rs:110), so the provers evaluate them on 2n points whatever the LDE blowup is and want 1 here
     uint32_t log_ce_blowup = 1;
     std::vector<std::pair<uint32_t, uint32_t>> mask;     // trace_arguments(): sorted (column, offset)
+    // Prover::prove checks the trace against every constraint (check_trace below) once the extension columns exist and throws,
+    // before the extension commitment, if one fails - ministark's debug-build `validate_constraints`.  Off by default: with it off
+    // the provers do exactly what they do without it.  The sharded prover refuses an AIR that has it on.
+    bool validate_trace = false;
     virtual AirProgramData build_program(uint64_t n, const std::vector<Felt> &challenges, const Felt &composition_coeff) = 0;
     // Optional, ahead of build_program: everything of the program that the challenges decide (its code, every constant but the powers
     // of the composition coefficient), so that the host builds it while the device extends and commits the extension trace and the
@@ -233,5 +237,16 @@ struct AirPublicInput;
 std::unique_ptr<Air> make_recursive_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_ce_blowup, uint64_t lde_offset);
 std::unique_ptr<Air> make_starknet_air(ss_ctx *ctx, const AirPublicInput &pi, uint32_t log_n, uint32_t log_ce_blowup, uint64_t lde_offset);
 std::vector<uint64_t> layout_air_tables(const Air &air);         // table descriptions of a layout AIR (host-side checks)
+
+// ---- the trace against its AIR on the device, constraint by constraint (ss_check_constraints; layout AIRs only).  cols: the base
+// columns then the extension columns, on the trace domain (n = 2^log_n rows each).  Returns the constraints that fail, in the
+// reference's order: index, StarkWare's name, the domain's name, the first row of the domain where the numerator is not zero and
+// the number of such rows.  Evaluates numerators on the trace domain only, so it does not depend on the LDE blowup factor.
+struct ConstraintFailure { uint32_t index; std::string name, domain; uint64_t first_row; uint32_t count; };
+std::vector<ConstraintFailure> check_trace(ss_ctx *ctx, Air &air, const std::vector<const uint64_t *> &cols, uint32_t log_n,
+                                           const std::vector<Felt> &challenges);
+// "trace does not satisfy the AIR: 3 constraints fail; first: #37 cpu/operands/res (every cycle) at row 19744, 1 row"
+std::string describe_failures(const std::vector<ConstraintFailure> &failures);
+std::vector<uint64_t> layout_air_check_program(Air &air, uint64_t n, const std::vector<Felt> &challenges);     // flat dump (air_layout.cpp)
 
 }  // namespace ssh

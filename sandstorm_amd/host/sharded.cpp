@@ -551,9 +551,16 @@ void ShardedProver::open(const Commitment &com, const std::vector<const uint64_t
     }
 }
 
+// the trace check reads whole columns on one device (check_trace); no rank of the sharded prover holds them
+void refuse_validation(const Air &air) {
+    if (air.validate_trace)
+        throw std::runtime_error("the sharded prover does not check the trace against the AIR: turn the " + air.name + " AIR's validation off (ssh_air_set_validation) or prove on one device");
+}
+
 bool ShardedProver::prove(const Digest &coin_seed, const std::map<uint32_t, uint64_t *> &my_base, const ShardedExtensionBuilder &build_extension,
                           uint64_t n, Proof *out) {
     Air &air = *claim_.air;
+    refuse_validation(air);
     const uint32_t R = comm_.world, r = comm_.rank;
     if (R & (R - 1)) throw std::runtime_error("the row blocks need a power-of-two number of ranks");
     const uint32_t lb = lde_log_blowup(opt_), log_n = log2u(n), log_N = log_n + lb;

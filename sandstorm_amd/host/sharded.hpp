@@ -64,6 +64,10 @@ using ShardedExtensionBuilder = std::function<std::map<uint32_t, uint64_t *>(con
 // the extension columns, in column order - the scans divide over the ranks and the owner's scatter falls away
 using ShardedExtensionBlocks = std::function<std::vector<uint64_t *>(const std::vector<Felt> &challenges)>;
 
+// throws, by name, for an AIR whose trace validation is on (Air::validate_trace): called by ShardedProver::prove and by the sharded
+// entry points before any device work or collective
+void refuse_validation(const Air &air);
+
 class ShardedProver {
 public:
     ShardedProver(ss_ctx *ctx, const Claim &claim, Transport &comm, const ProofOptions &opt = ProofOptions(), const Conventions &conv = Conventions())

@@ -86,6 +86,10 @@ def load():
         h.ssh_coin_free.argtypes = [C.c_void_p]
         h.ssh_coin_op.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64,
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        h.ssh_air_check_program.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+        h.ssh_air_set_validation.argtypes = [C.c_void_p, C.c_int]
+        h.ssh_check_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
         _host = h
     return _host
 
@@ -127,6 +131,12 @@ class HostAir:
         if self.h:
             load().ssh_air_destroy(self.h)
             self.h = None
+
+    def set_validation(self, on):
+        """Air::validate_trace: every prover that ends in the single-device Prover::prove (prove, prove_files, prove_files_device)
+        checks the trace against each constraint once the extension columns exist and raises, naming the first violated constraint
+        and its row, before it commits to them; the sharded provers refuse an AIR that has it on.  Off by default."""
+        _check(load().ssh_air_set_validation(self.h, 1 if on else 0))
 
 
 class RecursiveHostAir(HostAir):
@@ -179,6 +189,30 @@ class RecursiveHostAir(HostAir):
             # kind 0: periodic column number e (layouts.recursive calls its two "pedersen", layouts.starknet "column")
             specs.append((self.column_tag, e) if kind == 0 else ("periodic", num, den) if kind == 2 else ("inverse", e))
         return code, consts, n_slots, specs
+
+
+    def check_program(self, n, challenges):
+        """the AIR's check program (one CHECK per constraint over its bare numerator, in the reference's order; works without a
+        context) -> (code uint32[], consts uint64[*,4], n_slots, table_desc [offset, log2 length, ...], domains [(num, den)] with
+        num / den lists of zerofier factors (p, e))"""
+        ch = np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.uint64) for c in challenges]))
+        blob, ln = C.POINTER(C.c_uint64)(), C.c_uint64()
+        _check(load().ssh_air_check_program(self.h, n, ch.ctypes.data_as(C.POINTER(C.c_uint64)), len(challenges), C.byref(blob), C.byref(ln)))
+        words = [int(v) for v in np.ctypeslib.as_array(blob, shape=(ln.value,))]
+        load().ssh_free(blob)
+        it = iter(words)
+        n_instr = next(it)
+        code = np.array([next(it) for _ in range(2 * n_instr)], dtype=np.uint32)
+        n_consts = next(it)
+        consts = np.array([[next(it) for _ in range(4)] for _ in range(n_consts)], dtype=np.uint64).reshape(-1, 4)
+        n_slots = next(it)
+        desc = [next(it) for _ in range(2 * next(it))]
+        domains = []
+        for _ in range(next(it)):
+            num = [(next(it), next(it)) for _ in range(next(it))]
+            den = [(next(it), next(it)) for _ in range(next(it))]
+            domains.append((num, den))
+        return code, consts, n_slots, desc, domains
 
 
 class StarknetHostAir(RecursiveHostAir):
@@ -380,6 +414,27 @@ def build_extension_columns(ctx, layout, aux_cols, trace_len, challenges, check=
     _check(load().ssh_build_extension_columns(ctx.handle, 1 if layout == "recursive" else 2, be._ptr_array(aux_cols), trace_len,
                                               ch.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if check else 0, C.byref(h)))
     return HostMatrix(ctx, h, trace_len)
+
+
+def check_trace(ctx, air, cols, log_n, challenges):
+    """The trace against its AIR on the device, constraint by constraint (host/air_layout.cpp check_trace; ss_check_constraints).
+    air: RecursiveHostAir / StarknetHostAir made with this context; cols: the base columns then the extension columns on the
+    trace domain (device buffers of n = 2^log_n felts); challenges: the AIR's, as Montgomery limbs.  -> one
+    (index, name, domain, first_row, count) per constraint that fails, in the reference's order: its number and StarkWare's name, the
+    name of the domain it is enforced on, the first row of that domain where its numerator is not zero and how many there are.
+    An empty list: the trace satisfies the AIR."""
+    ch = np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.uint64) for c in challenges]))
+    n_bad, report = C.c_uint32(), C.c_void_p()
+    _check(load().ssh_check_trace(ctx.handle, air.h, be._ptr_array(cols), len(cols), log_n, ch.ctypes.data_as(C.POINTER(C.c_uint64)), len(challenges),
+                                  0, None, None, None, C.byref(n_bad), C.byref(report)))
+    text = C.string_at(report.value).decode() if report.value else ""
+    load().ssh_free(report)
+    out = []
+    for line in text.splitlines():
+        index, name, domain, first_row, count = line.split("\t")
+        out.append((int(index), name, domain, int(first_row), int(count)))
+    assert len(out) == n_bad.value
+    return out
 
 
 def build_extension_blocks(ctx, layout, aux_blocks, trace_len, rank, world, group, challenges, check=True):

@@ -16,7 +16,7 @@ SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "int": "c_int"
            "ss_perm_operand": "SsPermOperand", "ss_gather_job": "SsGatherJob", "uint16_t": "u16", "ss_trace_layout": "SsTraceLayout",
            "ss_trace_cell": "SsTraceCell", "ss_trace_rc_plan": "SsTraceRcPlan", "ss_trace_pedersen_layout": "SsTracePedersenLayout",
            "ss_trace_bitwise_layout": "SsTraceBitwiseLayout", "ss_trace_poseidon_layout": "SsTracePoseidonLayout",
-           "ss_trace_ec_op_layout": "SsTraceEcOpLayout", "ss_trace_ecdsa_layout": "SsTraceEcdsaLayout"}
+           "ss_trace_ec_op_layout": "SsTraceEcOpLayout", "ss_trace_ecdsa_layout": "SsTraceEcdsaLayout", "ss_check_domain": "SsCheckDomain"}
 
 
 def prototypes(text=None):
