@@ -258,8 +258,8 @@ enum {
     SS_OP_INV = 5,   /* acc[d] = 1 / acc[d]  (0 -> 0), operand ignored */
     SS_OP_ST = 6,    /* slot[payload] = acc[d]  */
     SS_OP_OUT = 7,   /* out[i] = acc[d]         */
-    SS_OP_CHECK = 10 /* check k = payload: acc[d] must be zero if this row is in domain k (ss_check_constraints only;
-                        ss_eval_quotient and ss_eval_quotient_rows refuse it; 8 and 9 are taken inside the library) */
+    SS_OP_CHECK = 10 /* check k = payload: acc[d] must be zero if this row is in domain k (ss_check_constraints and
+                        ss_check_constraints_gl64x3 only; the ss_eval_quotient family refuses it; 8 and 9 are taken inside the library) */
 };
 enum {
     SS_SRC_ACC = 0,    /* payload = accumulator index                                  */
@@ -411,6 +411,13 @@ ss_status ss_gather_rows_gl64(ss_ctx *ctx, const uint64_t *const *d_segments, ui
  * kernel for this field's experimental layout). */
 ss_status ss_eval_quotient_gl64x3(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_lde_cols, uint32_t ncols,
                                   uint32_t log_n, uint32_t log_blowup, uint64_t offset, uint64_t *d_out);
+/* ss_check_constraints over the cubic extension: the check program's format, domains and results are ss_check_constraints' (one
+ * SS_OP_CHECK k per constraint, no SS_OP_OUT; the trace domain x = w_n^r; first_row_out[k] = UINT64_MAX when constraint k holds), the
+ * constants three words each as for ss_eval_quotient_gl64x3.  A numerator is an element of Fq3: it violates iff any of its three
+ * coordinates is not zero.  ss_eval_quotient_gl64x3 goes on refusing SS_OP_CHECK. */
+ss_status ss_check_constraints_gl64x3(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_cols, uint32_t ncols,
+                                      uint32_t log_n, const ss_check_domain *domains, uint32_t n_checks, uint64_t *first_row_out,
+                                      uint32_t *count_out);
 ss_status ss_ood_eval_gl64x3(ss_ctx *ctx, const uint64_t *const *d_coeffs_bitrev, uint32_t ncols, uint32_t log_n,
                              const uint32_t *cell_col, const uint32_t *cell_off, uint32_t ncells, const uint64_t z[3],
                              uint64_t *out);

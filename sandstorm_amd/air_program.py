@@ -145,10 +145,23 @@ def lower(root, modulus, ext=False, symbols=None):
     place; when both children need code the right one goes to acc[dst+1] (or, past
     the fourth accumulator, the left one is parked in a scratch slot).  A node with
     several parents is computed once and kept in a slot until its last use."""
+    return _lower_roots([root], modulus, ext, symbols, False)
+
+
+def lower_checks(roots, modulus, ext=False, symbols=None):
+    """One program for many roots (ss_check_constraints / ss_check_constraints_gl64x3): code leaving roots[k] in accumulator 0
+    followed by CHECK k, for every k in order, and no OUT.  Use counts are taken over everything reachable from ANY root (a root
+    counts as one more use of its node), so a sub-expression that two constraints share - or a root that is one of a later root's
+    sub-expressions, or the same root twice - is computed once and parked in a slot until its last reader, across the CHECKs.
+    ext / symbols: as for lower()."""
+    return _lower_roots(list(roots), modulus, ext, symbols, True)
+
+
+def _lower_roots(roots, modulus, ext, symbols, checks):
     import sys
     sys.setrecursionlimit(max(100000, sys.getrecursionlimit()))
     prog = Program()
-    uses, seen, stack = {}, set(), [root]
+    uses, seen, stack = {}, set(), list(roots)
     while stack:
         n = stack.pop()
         if n._id in seen:
@@ -158,7 +171,8 @@ def lower(root, modulus, ext=False, symbols=None):
             if isinstance(a, Expr):
                 uses[a._id] = uses.get(a._id, 0) + 1
                 stack.append(a)
-    uses[root._id] = uses.get(root._id, 0) + 1
+    for root in roots:
+        uses[root._id] = uses.get(root._id, 0) + 1
     slot_of, free_slots = {}, []
 
     def alloc_slot():
@@ -264,8 +278,12 @@ def lower(root, modulus, ext=False, symbols=None):
             slot_of[n._id] = alloc_slot()
             emit(OP.ST, dst, 0, slot_of[n._id])
 
-    gen(root, 0)
-    emit(OP.OUT, 0)
+    for k, root in enumerate(roots):
+        gen(root, 0)
+        if checks:
+            emit(OP.CHECK, 0, 0, k)
+        else:
+            emit(OP.OUT, 0)
     return prog
 
 

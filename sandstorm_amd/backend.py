@@ -292,6 +292,27 @@ class Context:
                                _ptr_of(tables) if tables is not None else None, desc.ctypes.data_as(C.POINTER(C.c_uint32)), len(table_desc) // 2, n_slots)
         check(self.lib.ss_eval_quotient_gl64x3(self.handle, C.byref(prog), _ptr_array(lde_cols), len(lde_cols), log_n, log_blowup, int(offset), _ptr_of(out)))
 
+    def check_constraints_gl64x3(self, code, consts3, n_slots, tables, table_desc, cols, log_n, domains):
+        """ss_check_constraints_gl64x3: the trace columns `cols` (n = 2^log_n rows, the trace domain) against a program over Fq3 with one
+        CHECK k per constraint (code / consts3 / tables as for eval_quotient_gl64x3); domains[k] = (num, den), lists of zerofier factors
+        (p, e) = X^p - w_n^e.  -> (first_row uint64[n_checks] with 2^64 - 1 where constraint k holds, count uint32[n_checks])"""
+        code = np.ascontiguousarray(code, dtype=np.uint32)
+        consts = np.ascontiguousarray(consts3, dtype=np.uint64).reshape(-1, 3) if len(consts3) else np.zeros((1, 3), dtype=np.uint64)
+        desc = np.ascontiguousarray(table_desc if len(table_desc) else [0, 0], dtype=np.uint32)
+        prog = _lib.AirProgram(code.ctypes.data_as(C.POINTER(C.c_uint32)), len(code) // 2, consts.ctypes.data_as(C.POINTER(C.c_uint64)), len(consts3),
+                               _ptr_of(tables) if tables is not None else None, desc.ctypes.data_as(C.POINTER(C.c_uint32)), len(table_desc) // 2, n_slots)
+        doms = (_lib.CheckDomain * max(1, len(domains)))()
+        for k, (num, den) in enumerate(domains):
+            doms[k].n_num, doms[k].n_den = len(num), len(den)
+            for fs, dst in ((num, doms[k].num), (den, doms[k].den)):
+                for j, (p_, e) in enumerate(fs[:_lib.CHECK_MAX_FACTORS]):      # (a longer list is refused by the library, by its length)
+                    dst[j][0], dst[j][1] = int(p_), int(e)
+        first = np.zeros(max(1, len(domains)), dtype=np.uint64)
+        count = np.zeros(max(1, len(domains)), dtype=np.uint32)
+        check(self.lib.ss_check_constraints_gl64x3(self.handle, C.byref(prog), _ptr_array(cols), len(cols), log_n, doms, len(domains),
+                                                   first.ctypes.data_as(C.POINTER(C.c_uint64)), count.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return first[:len(domains)], count[:len(domains)]
+
     def ood_eval_gl64x3(self, coeff_cols, log_n, cell_col, cell_off, z):
         """P_{col_j}(z * w_n^{off_j}) for bit-reversed coefficient columns, z in Fq3 -> uint64[ncells, 3]"""
         cc, co = np.ascontiguousarray(cell_col, dtype=np.uint32), np.ascontiguousarray(cell_off, dtype=np.uint32)

@@ -3038,6 +3038,89 @@ ss_status ss_eval_quotient_gl64x3(ss_ctx *ctx, const ss_air_program *prog, const
     return SS_OK;
 }
 
+// The trace against its constraints one by one over the 64-bit field (goldilocks.hip: the checking instantiation of the Fq3
+// interpreter).  Always interpreted: the compiled kernel is the composition's.
+ss_status ss_check_constraints_gl64x3(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n,
+                                      const ss_check_domain *domains, uint32_t n_checks, uint64_t *first_row_out, uint32_t *count_out) {
+    if (!ctx || !prog || !d_cols || !domains || !first_row_out || !count_out) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!prog->code || prog->n_instr == 0 || n_checks == 0) return fail(SS_ERR_INVALID, "empty program");
+    if (!gl_valid_log(log_n)) return fail(SS_ERR_INVALID, "size out of range");
+    if (ncols > (uint32_t)MAX_COLS) return fail(SS_ERR_UNSUPPORTED, "ncols %u > %d", ncols, MAX_COLS);
+    if (has_null((const void *const *)d_cols, ncols)) return fail(SS_ERR_INVALID, "NULL column");
+    if (prog->n_consts && !prog->consts) return fail(SS_ERR_INVALID, "NULL constants");
+    if (prog->n_tables && (!prog->table_desc || !prog->d_tables)) return fail(SS_ERR_INVALID, "NULL tables");
+    const uint64_t n = 1ull << log_n;
+    // validate every operand before anything is launched: the kernel trusts the program
+    std::vector<uint8_t> seen(n_checks, 0);
+    for (uint32_t pc = 0; pc < prog->n_instr; ++pc) {
+        const uint32_t w0 = prog->code[2 * pc], w1 = prog->code[2 * pc + 1], op = w0 & 0xff, d = (w0 >> 8) & 0xf, kind = (w0 >> 12) & 0xf;
+        if (op == SS_OP_OUT) return fail(SS_ERR_INVALID, "instruction %u: OUT in a check program", pc);
+        if ((op > SS_OP_ST && op != SS_OP_CHECK) || d > 3) return fail(SS_ERR_INVALID, "instruction %u: bad opcode or accumulator", pc);
+        if (op == SS_OP_CHECK) {
+            if (w1 >= n_checks) return fail(SS_ERR_INVALID, "instruction %u: check %u out of range", pc, w1);
+            if (seen[w1]++) return fail(SS_ERR_INVALID, "instruction %u: check %u appears twice", pc, w1);
+        }
+        if (op == SS_OP_ST && w1 >= prog->n_slots) return fail(SS_ERR_INVALID, "instruction %u: slot %u out of range", pc, w1);
+        if (op > SS_OP_MUL) continue;
+        const bool ok = kind == SS_SRC_ACC ? w1 < 4 : kind == SS_SRC_SLOT ? w1 < prog->n_slots : kind == SS_SRC_CONST ? w1 < prog->n_consts
+                      : kind == SS_SRC_TRACE ? (w1 >> 24) < ncols : kind == SS_SRC_TABLE ? w1 < prog->n_tables : kind == SS_SRC_X;
+        if (!ok) return fail(SS_ERR_INVALID, "instruction %u: operand out of range", pc);
+    }
+    for (uint32_t k = 0; k < n_checks; ++k)
+        if (!seen[k]) return fail(SS_ERR_INVALID, "check %u does not appear in the program", k);
+    for (uint32_t k = 0; k < prog->n_consts; ++k)
+        if (!gl3_valid(prog->consts + 3 * (size_t)k)) return fail(SS_ERR_INVALID, "constant %u is not an element of the extension", k);
+    std::vector<uint32_t> tdesc(2 * (size_t)(prog->n_tables ? prog->n_tables : 1), 0);
+    for (uint32_t t = 0; t < prog->n_tables; ++t) {
+        if (prog->table_desc[2 * t + 1] > 30) return fail(SS_ERR_INVALID, "table %u: length out of range", t);
+        tdesc[2 * t] = prog->table_desc[2 * t];
+        tdesc[2 * t + 1] = (uint32_t)((1ull << prog->table_desc[2 * t + 1]) - 1ull);
+    }
+    std::vector<VmCheckDomain> doms(n_checks);
+    for (uint32_t k = 0; k < n_checks; ++k) {
+        const ss_check_domain &src = domains[k];
+        if (src.n_num > SS_CHECK_MAX_FACTORS || src.n_den > SS_CHECK_MAX_FACTORS)
+            return fail(SS_ERR_UNSUPPORTED, "check %u: a domain of %u numerator and %u denominator factors exceeds SS_CHECK_MAX_FACTORS = %u", k, src.n_num,
+                        src.n_den, SS_CHECK_MAX_FACTORS);
+        VmCheckDomain &dst = doms[k];
+        memset(&dst, 0, sizeof(dst));
+        dst.n_num = src.n_num; dst.n_den = src.n_den;
+        for (uint32_t j = 0; j < src.n_num; ++j) { dst.num[j][0] = (uint32_t)(src.num[j][0] & (n - 1)); dst.num[j][1] = (uint32_t)(src.num[j][1] & (n - 1)); }
+        for (uint32_t j = 0; j < src.n_den; ++j) { dst.den[j][0] = (uint32_t)(src.den[j][0] & (n - 1)); dst.den[j][1] = (uint32_t)(src.den[j][1] & (n - 1)); }
+    }
+    const uint64_t lanes = gl3_vm_lanes(n);
+    const size_t code_b = ((size_t)prog->n_instr * 8 + 31) / 32 * 32, const_b = ((size_t)(prog->n_consts ? prog->n_consts : 1) * 24 + 31) / 32 * 32;
+    const size_t tdesc_b = (tdesc.size() * 4 + 31) / 32 * 32, dom_b = (sizeof(VmCheckDomain) * n_checks + 31) / 32 * 32;
+    const size_t first_b = ((size_t)n_checks * 8 + 31) / 32 * 32, count_b = ((size_t)n_checks * 4 + 31) / 32 * 32;
+    ss_status st = ctx->ensure_scratch(const_b + code_b + tdesc_b + dom_b + first_b + count_b + 256);
+    if (st != SS_OK) return st;
+    st = ctx->ensure_scratch2((size_t)(prog->n_slots ? prog->n_slots : 1) * 3 * lanes * 8);
+    if (st != SS_OK) return st;
+    char *p = (char *)ctx->scratch;
+    uint64_t *d_consts = (uint64_t *)p; p += const_b;
+    uint32_t *d_code = (uint32_t *)p; p += code_b;
+    uint32_t *d_tdesc = (uint32_t *)p; p += tdesc_b;
+    VmCheckDomain *d_doms = (VmCheckDomain *)p; p += dom_b;
+    uint64_t *d_first = (uint64_t *)p; p += first_b;
+    uint32_t *d_count = (uint32_t *)p;
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(d_code, prog->code, (size_t)prog->n_instr * 8, hipMemcpyHostToDevice, s));
+    if (prog->n_consts) HIP_TRY(hipMemcpyAsync(d_consts, prog->consts, (size_t)prog->n_consts * 24, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_tdesc, tdesc.data(), tdesc.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_doms, doms.data(), sizeof(VmCheckDomain) * n_checks, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_first, 0xff, (size_t)n_checks * 8, s));
+    HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)n_checks * 4, s));
+    {
+        ss_ctx::Scope prof(ctx, SS_PROF_QUOTIENT);
+        HIP_TRY(launch_gl3_vm_check(s, d_code, prog->n_instr, d_consts, prog->d_tables, d_tdesc, d_cols, ncols, (uint64_t *)ctx->scratch2,
+                                    gl_root_of_unity_host(log_n), n, d_doms, d_first, d_count));
+    }
+    HIP_TRY(hipMemcpyAsync(first_row_out, d_first, (size_t)n_checks * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(count_out, d_count, (size_t)n_checks * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SS_OK;
+}
+
 ss_status ss_ood_eval_gl64x3(ss_ctx *ctx, const uint64_t *const *d_coeffs_bitrev, uint32_t ncols, uint32_t log_n, const uint32_t *cell_col,
                              const uint32_t *cell_off, uint32_t ncells, const uint64_t z[3], uint64_t *out) {
     if (!ctx || !d_coeffs_bitrev || !z || (ncells && (!cell_col || !cell_off || !out))) return fail(SS_ERR_INVALID, "NULL argument");

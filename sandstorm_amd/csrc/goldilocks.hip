@@ -15,6 +15,7 @@
 // Every operation here is linear in the data (data times coefficients this file owns), so element images in Montgomery
 // form (arkworks' Fp64 in memory) pass through unchanged.
 #include <hip/hip_runtime.h>
+#include "../../include/sandstorm_hip.h"
 #include "kernels.h"
 #include "gl64.h"
 #include "gl_ntt.h"
@@ -459,13 +460,55 @@ struct Gl3VmArgs {
     uint32_t n_instr, log_blowup;
     uint64_t N;
 };
-__global__ __launch_bounds__(256) void gl3_vm_kernel(Gl3VmArgs a) {
+// ---- the checking instantiation (ss_check_constraints_gl64x3): one CHECK k per constraint instead of one OUT, the domain is the trace
+// domain itself (x = w_n^row, no offset, no blowup) and nothing is written but, per violated constraint, its first row and its number of
+// rows.  Whether row r belongs to domain k is the integer rule of the 252-bit check (quotient.hip vm_row_in_domain): the factor
+// X^p - w^e vanishes at w^r iff p r = e (mod n); the row is in the domain iff some denominator factor vanishes and no numerator factor does.
+struct Gl3CheckArgs {
+    const VmCheckDomain *domains;       // [n_checks]
+    unsigned long long *first_row;      // [n_checks], preset to ~0
+    uint32_t *count;                    // [n_checks], preset to 0
+};
+__device__ __forceinline__ bool gl3_row_in_domain(const VmCheckDomain &d, uint32_t row, uint32_t nmask) {
+    bool num = false, den = false;
+    for (uint32_t j = 0; j < d.n_num; ++j) num |= (((uint64_t)d.num[j][0] * row - d.num[j][1]) & nmask) == 0;
+    for (uint32_t j = 0; j < d.n_den; ++j) den |= (((uint64_t)d.den[j][0] * row - d.den[j][1]) & nmask) == 0;
+    return den && !num;
+}
+// One CHECK.  The numerator is an element of Fq3: it is zero iff ALL three canonical coordinates are.  Only a violating lane asks
+// for the domain; then the wave reduces (smallest violating row, violating lanes) with 12 shuffles and its first lane issues at most one
+// atomic pair - none on a clean trace.  Every lane of the wave gets here (the point loop has a workgroup-uniform trip count in this
+// instantiation, the program counter is wave-uniform); a lane whose point lies beyond n takes part as "no violation".
+__device__ __forceinline__ void gl3_check(const Gl3CheckArgs &c, uint32_t k, const Gl3 &v, bool live, uint32_t row, uint32_t nmask) {
+    bool bad = live && (gl_canon(v.c[0]) | gl_canon(v.c[1]) | gl_canon(v.c[2])) != 0;
+    if (bad) bad = gl3_row_in_domain(c.domains[k], row, nmask);
+    uint32_t first = bad ? row : 0xffffffffu;
+    int cnt = bad ? 1 : 0;
+    for (int m = 32; m; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)first, m, 64);
+        first = o < first ? o : first;
+        cnt += __shfl_xor(cnt, m, 64);
+    }
+    if ((threadIdx.x & 63u) == 0 && cnt) {
+        atomicMin(c.first_row + k, (unsigned long long)first);
+        atomicAdd(c.count + k, (uint32_t)cnt);
+    }
+}
+
+// the interpreter's body: CHECK = false is ss_eval_quotient_gl64x3's kernel, CHECK = true ss_check_constraints_gl64x3's.  The
+// arguments come BY VALUE: taken by reference, <false> compiles to other code than the kernel had before it was a template (56
+// scalar registers instead of 88: the kernel arguments re-read where they had been kept) - by value it keeps its resource line
+template <bool CHECK>
+__device__ __forceinline__ void gl3_vm_body(Gl3VmArgs a, Gl3CheckArgs chk) {
     typedef const uint32_t __attribute__((address_space(4))) *const_u32;
     const_u32 code = (const_u32)(uintptr_t)a.code, tdesc = (const_u32)(uintptr_t)a.tdesc;
     const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x, lane = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     const uint64_t wstep = gl_pow_dev(a.w, lanes);
     uint64_t x = gl_mul(a.offset, gl_pow_dev(a.w, lane));
-    for (uint64_t i = lane; i < a.N; i += lanes, x = gl_mul(x, wstep)) {
+    // checking: every lane of a workgroup makes as many sweeps as its first lane, whose point is i - threadIdx.x (they differ only
+    // where N < 256); a lane past N reads wrapped indices (trace cells and tables are masked, the slot file is indexed by the lane)
+    // and votes "no violation"
+    for (uint64_t i = lane; (CHECK ? i - threadIdx.x : i) < a.N; i += lanes, x = gl_mul(x, wstep)) {
         Gl3 acc0 = {{0, 0, 0}}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
         for (uint32_t pc = 0; pc < a.n_instr; ++pc) {
             const uint32_t w0 = code[2 * pc], w1 = code[2 * pc + 1];
@@ -506,9 +549,20 @@ __global__ __launch_bounds__(256) void gl3_vm_kernel(Gl3VmArgs a) {
             default: SS_GL3_VM_ON(acc3) break;
             }
 #undef SS_GL3_VM_ON
+            if (CHECK && op == SS_OP_CHECK) {          // (the C ABI lets no OUT into a check program: case 7 above is never taken here)
+                const uint32_t nmask = (uint32_t)a.N - 1u;
+                switch (d) {
+                case 0: gl3_check(chk, w1, acc0, i < a.N, (uint32_t)i, nmask); break;
+                case 1: gl3_check(chk, w1, acc1, i < a.N, (uint32_t)i, nmask); break;
+                case 2: gl3_check(chk, w1, acc2, i < a.N, (uint32_t)i, nmask); break;
+                default: gl3_check(chk, w1, acc3, i < a.N, (uint32_t)i, nmask); break;
+                }
+            }
         }
     }
 }
+__global__ __launch_bounds__(256) void gl3_vm_kernel(Gl3VmArgs a) { gl3_vm_body<false>(a, Gl3CheckArgs{nullptr, nullptr, nullptr}); }
+__global__ __launch_bounds__(256) void gl3_vm_check_kernel(Gl3VmArgs a, Gl3CheckArgs c) { gl3_vm_body<true>(a, c); }
 uint32_t gl3_vm_lanes(uint64_t N) { return gl_blocks(N, 256, 4096) * 256u; }
 hipError_t launch_gl3_vm(hipStream_t st, const uint32_t *d_code, uint32_t n_instr, const uint64_t *d_consts, const uint64_t *d_tables,
                          const uint32_t *d_tdesc, const uint64_t *const *cols, uint32_t ncols, uint64_t *d_slots, uint64_t *d_out, uint64_t offset,
@@ -518,6 +572,20 @@ hipError_t launch_gl3_vm(hipStream_t st, const uint32_t *d_code, uint32_t n_inst
     for (int c = 0; c < MAX_COLS; ++c) a.cols[c] = c < (int)ncols ? cols[c] : nullptr;
     a.offset = offset; a.w = w; a.n_instr = n_instr; a.log_blowup = log_blowup; a.N = N;
     hipLaunchKernelGGL(gl3_vm_kernel, dim3(gl3_vm_lanes(N) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+// the trace domain (n a power of two, x_r = w^r with w = w_n); gl3_vm_lanes(n) lanes, the slot file sized for them; the three arrays
+// hold n_checks entries, first_row preset to ~0 and count to 0
+hipError_t launch_gl3_vm_check(hipStream_t st, const uint32_t *d_code, uint32_t n_instr, const uint64_t *d_consts, const uint64_t *d_tables,
+                               const uint32_t *d_tdesc, const uint64_t *const *cols, uint32_t ncols, uint64_t *d_slots, uint64_t w, uint64_t n,
+                               const VmCheckDomain *d_domains, uint64_t *d_first_row, uint32_t *d_count) {
+    Gl3VmArgs a;
+    a.code = d_code; a.consts = d_consts; a.tables = d_tables; a.tdesc = d_tdesc; a.slots = d_slots; a.out = nullptr;
+    for (int c = 0; c < MAX_COLS; ++c) a.cols[c] = c < (int)ncols ? cols[c] : nullptr;
+    a.offset = 1; a.w = w; a.n_instr = n_instr; a.log_blowup = 0; a.N = n;
+    Gl3CheckArgs c;
+    c.domains = d_domains; c.first_row = (unsigned long long *)d_first_row; c.count = d_count;
+    hipLaunchKernelGGL(gl3_vm_check_kernel, dim3(gl3_vm_lanes(n) / 256), dim3(256), 0, st, a, c);
     return hipGetLastError();
 }
 

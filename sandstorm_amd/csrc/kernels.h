@@ -323,5 +323,9 @@ struct VmCheckDomain {
 };
 hipError_t launch_quotient_vm_check(hipStream_t st, const uint32_t *d_code, uint32_t n_entries, Fp *d_slots, uint64_t lanes, const Fp &w,
                                     const Fp &wstep, uint64_t npoints, const VmCheckDomain *d_domains, uint64_t *d_first_row, uint32_t *d_count);
+// the same over the 64-bit field's cubic extension (goldilocks.hip gl3_vm_check_kernel): gl3_vm_lanes(n) lanes, x_r = w^r
+hipError_t launch_gl3_vm_check(hipStream_t st, const uint32_t *d_code, uint32_t n_instr, const uint64_t *d_consts, const uint64_t *d_tables,
+                               const uint32_t *d_tdesc, const uint64_t *const *cols, uint32_t ncols, uint64_t *d_slots, uint64_t w, uint64_t n,
+                               const VmCheckDomain *d_domains, uint64_t *d_first_row, uint32_t *d_count);
 
 }  // namespace ss

@@ -60,6 +60,9 @@ class Air:
     # (n, challenges, alpha, tables) -> Expr root; tables: layouts.plain.Tables (or anything with .specs/.device_tables/.value_at)
     composition: object = None
     make_tables: object = None      # (n, log_blowup) -> tables
+    # optional: (n, challenges, statement) -> (check Program, [(num, den)] factor lists, constraint names, domain names): what
+    # check_trace and a validating prover evaluate (layouts.plain.check_program)
+    checks: object = None
 
 
 @dataclass
@@ -171,13 +174,45 @@ def _powers3(a, count):
     return out
 
 
+# ---- the trace against its AIR ------------------------------------------------------------------------------------------------
+def check_trace(ctx, air: Air, cols, challenges, statement=None):
+    """The trace against the AIR on the device, constraint by constraint (ss_check_constraints_gl64x3; ministark's debug-build
+    `validate_constraints`).  cols: the base columns then the extension trace's coordinate columns on the trace domain (device,
+    n values each); challenges: the AIR's, in Fq3.  -> one (index, name, domain, first_row, count) per constraint that fails, in the
+    reference's order: its number and StarkWare's name, the name of the domain it is enforced on, the first row of that domain where
+    its numerator is not zero and how many there are.  An empty list: the trace satisfies the AIR."""
+    if air.checks is None:
+        raise ValueError("the AIR '%s' has no check program" % air.name)
+    cols = list(cols)
+    if len(cols) != air.num_base + air.num_ext:
+        raise ValueError("%d columns for an AIR of %d base and %d extension coordinate columns" % (len(cols), air.num_base, air.num_ext))
+    n = int(cols[0].shape[0]) if hasattr(cols[0], "shape") else int(cols[0].nbytes // 8)
+    prog, domains, names, domain_names = air.checks(n, [tuple(int(v) for v in c) for c in challenges], statement)
+    first, count = ctx.check_constraints_gl64x3(np.array(prog.code, dtype=np.uint32), np.array(prog.consts, dtype=np.uint64).reshape(-1, 3),
+                                                prog.n_slots, None, [], cols, n.bit_length() - 1, domains)
+    return [(k, names[k], domain_names[k], int(first[k]), int(count[k])) for k in range(len(domains)) if count[k]]
+
+
+def describe_failures(failures):
+    """the C++ host's wording (host/air_layout.cpp describe_failures)"""
+    if not failures:
+        return "the trace satisfies the AIR"
+    index, name, domain, first_row, count = failures[0]
+    return "trace does not satisfy the AIR: %d %s; first: #%d %s (%s) at row %d, %d %s" % (
+        len(failures), "constraint fails" if len(failures) == 1 else "constraints fail", index, name, domain, first_row, count,
+        "row" if count == 1 else "rows")
+
+
 # ---- prover ----------------------------------------------------------------------------------------------------------------------
 class Prover:
     """columns are torch int64 tensors on the device; ctx: a backend.Context bound to the SAME stream torch works on - an explicit
     torch.cuda.Stream made current (torch's default stream has handle 0, which the C ABI reads as "the context's own stream")"""
 
-    def __init__(self, ctx, air: Air, options: Options = None):
-        self.ctx, self.air, self.opt = ctx, air, options or Options()
+    def __init__(self, ctx, air: Air, options: Options = None, validate=False):
+        """validate: prove() checks the base and the fresh extension columns against every constraint with the proof's own challenges
+        (check_trace) and raises ValueError naming the first one that fails, before it commits to the extension trace.  Off: the
+        launches and the proof are what they are without it"""
+        self.ctx, self.air, self.opt, self.validate = ctx, air, options or Options(), bool(validate)
         if self.opt.hash not in ("blake2s", "sha256"):
             raise ValueError("Options.hash: 'blake2s' or 'sha256'")
         self._row_hash, self._tree = (be.HASH_SHA256, be.TREE_SHA256) if self.opt.hash == "sha256" else (be.HASH_BLAKE2S, be.TREE_BLAKE2S)
@@ -196,9 +231,9 @@ class Prover:
         paths, _ = self.ctx.merkle_open(nodes, None, n_rows, positions)
         return Opening(rows, paths)
 
-    def prove(self, seed: bytes, base_cols, build_extension, tables=None, statement=None):
+    def prove(self, seed: bytes, base_cols, build_extension, tables=None, statement=None, validate=None):
         """base_cols: the base columns [n] (device); build_extension(challenges) -> the extension trace's coordinate columns.
-        statement: passed through to air.composition (hints come from it)"""
+        statement: passed through to air.composition (hints come from it).  validate: this call's override of the prover's switch"""
         import torch
         ctx, air, opt = self.ctx, self.air, self.opt
         n = base_cols[0].shape[0]
@@ -221,6 +256,10 @@ class Prover:
         coin.reseed_with_digest(proof.base_root)
         challenges = [coin.draw_fq3() for _ in range(air.num_challenges)]
         ext_cols = list(build_extension(challenges)) if air.num_ext else []
+        if self.validate if validate is None else validate:
+            bad = check_trace(ctx, air, list(base_cols) + ext_cols, challenges, statement)
+            if bad:
+                raise ValueError(describe_failures(bad))
         ext_ev, ext_co = extend(ext_cols) if ext_cols else ([], [])
         if ext_cols:
             proof.ext_root, ext_nodes = self._commit(ext_ev, N)
@@ -563,18 +602,19 @@ def plain_base_trace_on_device(ctx, trace_bin, memory_bin, pi, out=None):
     return out
 
 
-def prove_files(ctx, trace_bin, memory_bin, pi, seed, options=None, out=None, want_times=False):
+def prove_files(ctx, trace_bin, memory_bin, pi, seed, options=None, out=None, want_times=False, validate=False):
     """the claim from the files in ONE call, what the reference's "Proof generated in" timer wraps (cli/src/main.rs:186-202): the base
     columns made on the device, the extension column built and the proof written by the C++ host (hostlib.gl_prove_files); only the
     plain AIR's lowering comes from Python.  -> the Proof Prover.prove writes from base_trace's columns with the same seed and statement
-    (with want_times: (Proof, {"trace_gen_s", "total_s"}))"""
+    (with want_times: (Proof, {"trace_gen_s", "total_s"})).  validate: the C++ host checks the trace against the AIR before the extension
+    commitment (check_trace's report, Prover's message, raised as SandstormHipError)"""
     import torch
     from . import hostlib
     n = F.CYCLE_HEIGHT * (len(trace_bin) // 24)
     if out is None:
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         out = [torch.empty(n, dtype=torch.int64, device=dev) for _ in range(F.NUM_BASE_COLUMNS)]
-    proof, times = hostlib.gl_prove_files(ctx, plain_air(), options or Options(), seed, trace_bin, memory_bin, pi, out)
+    proof, times = hostlib.gl_prove_files(ctx, plain_air(), options or Options(), seed, trace_bin, memory_bin, pi, out, validate=validate)
     return (proof, times) if want_times else proof
 
 
@@ -584,4 +624,7 @@ def plain_air():
     def composition(n, challenges, alpha, tables, pi):
         hints = F.Hints.from_public_input(pi, challenges, n)
         return F.composition(n, hints, challenges, alpha, tables)
-    return Air("plain", F.NUM_BASE_COLUMNS, 3 * F.NUM_EXTENSION_COLUMNS, F.NUM_CHALLENGES, F.mask(), composition, lambda n, lb: F.Tables(n, lb))
+
+    def checks(n, challenges, pi):
+        return F.check_program(n, F.Hints.from_public_input(pi, challenges, n), challenges)
+    return Air("plain", F.NUM_BASE_COLUMNS, 3 * F.NUM_EXTENSION_COLUMNS, F.NUM_CHALLENGES, F.mask(), composition, lambda n, lb: F.Tables(n, lb), checks)

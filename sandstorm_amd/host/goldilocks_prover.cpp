@@ -151,9 +151,37 @@ using DevP = std::unique_ptr<Dev>;
 struct Commitment { DevP nodes; Digest root; };
 }  // namespace
 
+std::vector<ConstraintFailure> check_trace(ss_ctx *ctx, const CheckBlob &check, const std::vector<const uint64_t *> &cols, uint32_t log_n) {
+    const size_t n_checks = check.domains.size();
+    if (!n_checks || check.names.size() != n_checks || check.domain_names.size() != n_checks) throw std::runtime_error("check program: one domain and two names per check");
+    ss_air_program prog;
+    memset(&prog, 0, sizeof prog);
+    static const uint64_t no_consts[3] = {0, 0, 0};
+    static const uint32_t no_desc[2] = {0, 0};
+    prog.code = check.code.data(); prog.n_instr = (uint32_t)(check.code.size() / 2);
+    prog.consts = check.consts.empty() ? no_consts : check.consts.data(); prog.n_consts = (uint32_t)(check.consts.size() / 3);
+    prog.d_tables = check.d_tables; prog.table_desc = check.table_desc.empty() ? no_desc : check.table_desc.data();
+    prog.n_tables = (uint32_t)(check.table_desc.size() / 2);
+    prog.n_slots = check.n_slots;
+    std::vector<uint64_t> first(n_checks, 0);
+    std::vector<uint32_t> count(n_checks, 0);
+    ok(ss_check_constraints_gl64x3(ctx, &prog, cols.data(), (uint32_t)cols.size(), log_n, check.domains.data(), (uint32_t)n_checks, first.data(), count.data()));
+    std::vector<ConstraintFailure> bad;
+    for (size_t k = 0; k < n_checks; ++k)
+        if (count[k]) bad.push_back(ConstraintFailure{(uint32_t)k, check.names[k], check.domain_names[k], first[k], count[k]});
+    return bad;
+}
+std::string describe_failures(const std::vector<ConstraintFailure> &f) {
+    if (f.empty()) return "the trace satisfies the AIR";
+    const ConstraintFailure &a = f.front();
+    return "trace does not satisfy the AIR: " + std::to_string(f.size()) + (f.size() == 1 ? " constraint fails" : " constraints fail") + "; first: #" +
+           std::to_string(a.index) + " " + a.name + " (" + a.domain + ") at row " + std::to_string(a.first_row) + ", " + std::to_string(a.count) +
+           (a.count == 1 ? " row" : " rows");
+}
+
 Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &statement_digest, const std::vector<const uint64_t *> &base_cols,
             uint64_t n, const std::vector<std::pair<uint32_t, uint32_t>> &mask, uint32_t num_challenges, uint32_t num_ext,
-            const ExtensionBuilder &build_extension, const ProgramBuilder &build_program) {
+            const ExtensionBuilder &build_extension, const ProgramBuilder &build_program, const CheckBuilder &build_check) {
     if (!n || (n & (n - 1))) throw std::runtime_error("trace length: a power of two");
     if (opt.log_blowup != 1) throw std::runtime_error("the composition split (even / odd coefficients) is written for blowup 2");
     uint32_t log_n = 0;
@@ -211,11 +239,20 @@ Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &s
     if (num_ext) {
         const std::vector<const uint64_t *> ext_cols = build_extension(challenges);
         if (ext_cols.size() != num_ext) throw std::runtime_error("the extension builder returned another number of coordinate columns");
+        if (build_check) {                                  // the caller's base columns and the fresh extension columns, with this proof's challenges
+            std::vector<const uint64_t *> all(base_cols.begin(), base_cols.end());
+            all.insert(all.end(), ext_cols.begin(), ext_cols.end());
+            const std::vector<ConstraintFailure> bad = check_trace(ctx, build_check(challenges), all, log_n);
+            if (!bad.empty()) throw std::runtime_error(describe_failures(bad));
+        }
         extend(ext_cols, &trace_ev, &trace_co);
         ext_com = commit(std::vector<const uint64_t *>(trace_ev.begin() + nbase, trace_ev.end()), 1, N);
         proof.has_ext = true;
         proof.ext_root = ext_com.root;
         coin.reseed_with_digest(proof.ext_root);
+    } else if (build_check) {                               // an AIR without an extension trace: the base columns alone
+        const std::vector<ConstraintFailure> bad = check_trace(ctx, build_check(challenges), base_cols, log_n);
+        if (!bad.empty()) throw std::runtime_error(describe_failures(bad));
     }
     // 3-4. composition: the lowered program over the LDE domain, then H = H0(x^2) + x H1(x^2) as six coordinate columns
     const Fq3 alpha = coin.draw_fq3();

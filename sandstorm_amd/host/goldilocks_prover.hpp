@@ -4,10 +4,12 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "coin.hpp"
+#include "gl_check_blob.hpp"
 #include "../../include/sandstorm_hip.h"
 
 namespace ssh {
@@ -51,10 +53,23 @@ struct ProgramData {
 };
 using ProgramBuilder = std::function<ProgramData(const std::vector<Fq3> &challenges, const Fq3 &alpha)>;
 
+// The trace against its AIR (ss_check_constraints_gl64x3; ministark's debug-build `validate_constraints`): the layout's check program
+// for the drawn challenges - one SS_OP_CHECK per constraint over its bare numerator -, the per-check domains and the names
+// (gl_check_blob.hpp).  cols: the base columns then the extension trace's coordinate columns on the trace domain, n = 2^log_n values
+// each.  -> the constraints that fail, in the program's order
+using CheckBuilder = std::function<CheckBlob(const std::vector<Fq3> &challenges)>;
+struct ConstraintFailure { uint32_t index; std::string name, domain; uint64_t first_row; uint32_t count; };
+std::vector<ConstraintFailure> check_trace(ss_ctx *ctx, const CheckBlob &check, const std::vector<const uint64_t *> &cols, uint32_t log_n);
+// "trace does not satisfy the AIR: 3 constraints fail; first: #37 cpu/operands/res (every cycle) at row 19744, 1 row" (the 252-bit
+// path's wording, host/air_layout.cpp)
+std::string describe_failures(const std::vector<ConstraintFailure> &failures);
+
 Digest transcript_seed(const Digest &seed, const Options &opt, uint64_t trace_len, const Digest &statement_digest);
 Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &statement_digest, const std::vector<const uint64_t *> &base_cols,
             uint64_t n, const std::vector<std::pair<uint32_t, uint32_t>> &mask, uint32_t num_challenges, uint32_t num_ext,
-            const ExtensionBuilder &build_extension, const ProgramBuilder &build_program);
+            const ExtensionBuilder &build_extension, const ProgramBuilder &build_program, const CheckBuilder &build_check = nullptr);
+// build_check (optional): the base and the fresh extension columns are checked against it with the proof's own challenges before the
+// extension commitment; a trace that fails throws describe_failures' message.  Without it the proof's launches are what they were.
 
 }  // namespace gl
 }  // namespace ssh

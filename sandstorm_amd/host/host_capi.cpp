@@ -812,12 +812,26 @@ int ssh_prove_files_sharded_device(ss_ctx *ctx, int layout, const uint8_t *trace
 typedef int (*ssh_gl_extension_cb)(void *user, const uint64_t *challenges, uint32_t nchallenges, uint64_t **d_cols_out);
 typedef int (*ssh_gl_program_cb)(void *user, const uint64_t *challenges, uint32_t nchallenges, const uint64_t *alpha, const uint64_t **blob_out,
                                  uint64_t *blob_len);
+// check_cb (the *_checked entries and ssh_gl_check_trace): the layout's check program, domains and names for the challenges, as the
+// blob host/gl_check_blob.hpp documents and parses; the callee owns it until the next call.  NULL: no check.
+typedef int (*ssh_gl_check_cb)(void *user, const uint64_t *challenges, uint32_t nchallenges, const uint64_t **blob_out, uint64_t *blob_len);
 namespace {
+gl::CheckBuilder gl_check_builder(ssh_gl_check_cb check_cb, void *user) {
+    if (!check_cb) return nullptr;
+    return [check_cb, user](const std::vector<gl::Fq3> &ch) {
+        std::vector<uint64_t> f;
+        for (auto &c : ch) f.insert(f.end(), c.begin(), c.end());
+        const uint64_t *blob = nullptr;
+        uint64_t len = 0;
+        if (check_cb(user, f.data(), (uint32_t)ch.size(), &blob, &len) != 0) throw std::runtime_error("check callback failed");
+        return gl::parse_check_blob(blob, len);
+    };
+}
 // the body ssh_gl_prove and ssh_gl_prove_files_device share: the proof for these columns as the u64 blob described above; `extension`
 // makes the extension trace's coordinate columns for the drawn challenges
 void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base, uint32_t nbase,
                    uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, const gl::ExtensionBuilder &extension,
-                   ssh_gl_program_cb prog_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+                   ssh_gl_program_cb prog_cb, ssh_gl_check_cb check_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
     {
         gl::Options opt;
         opt.num_queries = options[0]; opt.log_blowup = options[1]; opt.grinding = options[2]; opt.fold = options[3]; opt.max_remainder = options[4];
@@ -845,7 +859,7 @@ void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32
                 pd.consts.assign(q, q + 3 * n_consts); q += 3 * n_consts;
                 for (uint64_t i = 0; i < 2 * n_tables; ++i) pd.table_desc.push_back((uint32_t)*q++);
                 return pd;
-            });
+            }, gl_check_builder(check_cb, user));
         std::vector<uint64_t> out{p.trace_len, p.pow_nonce, p.has_ext ? 1ull : 0ull, p.fri_layers.size()};
         auto digest = [&](const Digest &d) { uint64_t w[4]; memcpy(w, d.data(), 32); out.insert(out.end(), w, w + 4); };
         digest(p.base_root); digest(p.ext_root); digest(p.comp_root);
@@ -871,9 +885,11 @@ void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32
     }
 }
 }  // namespace
-int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base,
-                 uint32_t nbase, uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, ssh_gl_extension_cb ext_cb,
-                 ssh_gl_program_cb prog_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+// ssh_gl_prove with the trace checked against the AIR before the extension commitment (gl::prove's build_check): a trace that fails
+// ends the call with "trace does not satisfy the AIR: ..."; check_cb = NULL is ssh_gl_prove
+int ssh_gl_prove_checked(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base,
+                         uint32_t nbase, uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, ssh_gl_extension_cb ext_cb,
+                         ssh_gl_program_cb prog_cb, ssh_gl_check_cb check_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
     try {
         if (!ctx || !options || !seed || !statement_digest || !d_base || !mask || !prog_cb || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove: NULL argument");
         gl_prove_blob(ctx, options, seed, statement_digest, d_base, nbase, n, mask, nmask, num_challenges, num_ext,
@@ -883,7 +899,33 @@ int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32],
                 for (auto &c : ch) f.insert(f.end(), c.begin(), c.end());
                 if (!ext_cb || ext_cb(user, f.data(), (uint32_t)ch.size(), cols.data()) != 0) throw std::runtime_error("extension callback failed");
                 return std::vector<const uint64_t *>(cols.begin(), cols.end());
-            }, prog_cb, user, proof_blob, proof_len);
+            }, prog_cb, check_cb, user, proof_blob, proof_len);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int ssh_gl_prove(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base,
+                 uint32_t nbase, uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, ssh_gl_extension_cb ext_cb,
+                 ssh_gl_program_cb prog_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+    return ssh_gl_prove_checked(ctx, options, seed, statement_digest, d_base, nbase, n, mask, nmask, num_challenges, num_ext, ext_cb, prog_cb, nullptr, user,
+                                proof_blob, proof_len);
+}
+// The trace against the AIR as a call of its own (gl::check_trace): d_cols = the base columns then the extension trace's coordinate
+// columns on the trace domain, challenges 3 u64 each.  *n_failures = how many constraints fail; *report (optional; ssh_free) = one line
+// per failing constraint: "index\tname\tdomain\tfirst row\tcount".
+int ssh_gl_check_trace(ss_ctx *ctx, const uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n, const uint64_t *challenges, uint32_t nchallenges,
+                       ssh_gl_check_cb check_cb, void *user, uint32_t *n_failures, char **report) {
+    try {
+        if (!ctx || !d_cols || !check_cb || !n_failures || (nchallenges && !challenges)) throw std::runtime_error("ssh_gl_check_trace: NULL argument");
+        std::vector<gl::Fq3> ch(nchallenges);
+        for (uint32_t i = 0; i < nchallenges; ++i) ch[i] = gl::Fq3{challenges[3 * i], challenges[3 * i + 1], challenges[3 * i + 2]};
+        const std::vector<gl::ConstraintFailure> bad = gl::check_trace(ctx, gl_check_builder(check_cb, user)(ch), std::vector<const uint64_t *>(d_cols, d_cols + ncols), log_n);
+        *n_failures = (uint32_t)bad.size();
+        if (report) {
+            std::string text;
+            for (auto &b : bad) text += std::to_string(b.index) + "\t" + b.name + "\t" + b.domain + "\t" + std::to_string(b.first_row) + "\t" + std::to_string(b.count) + "\n";
+            *report = (char *)malloc(text.size() + 1);
+            memcpy(*report, text.c_str(), text.size() + 1);
+        }
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }
@@ -911,10 +953,12 @@ int ssh_gl_trace_last_stats(uint64_t out[1]) {
 // goldilocks.plain_extension_on_device does; refused if the range-check product does not close), then ssh_gl_prove's proof blob.  The
 // composition program still comes through prog_cb (the plain AIR is lowered in Python); mask as for ssh_gl_prove.  times_out (optional,
 // 2 doubles) as ssh_prove_files_device: until the columns were final, and the whole call.
-int ssh_gl_prove_files_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len, uint64_t n_steps,
-                              const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint64_t *const d_cols[5], const uint32_t options[6],
-                              const uint8_t seed[32], const uint8_t statement_digest[32], const uint32_t *mask, uint32_t nmask, ssh_gl_program_cb prog_cb, void *user,
-                              double *times_out, uint64_t **proof_blob, uint64_t *proof_len) {
+// ssh_gl_prove_files_device_checked: the same with check_cb (NULL: no check).  The files' refusals and "the range-check permutation does
+// not close" come first and read as they do without it; the check runs on the finished base and extension columns.
+int ssh_gl_prove_files_device_checked(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len, uint64_t n_steps,
+                                      const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint64_t *const d_cols[5], const uint32_t options[6],
+                                      const uint8_t seed[32], const uint8_t statement_digest[32], const uint32_t *mask, uint32_t nmask, ssh_gl_program_cb prog_cb,
+                                      ssh_gl_check_cb check_cb, void *user, double *times_out, uint64_t **proof_blob, uint64_t *proof_len) {
     struct Columns {                                                 // the extension trace's three coordinate columns: this call's own
         ss_ctx *ctx; uint64_t *col[3] = {nullptr, nullptr, nullptr};
         ~Columns() { (void)ss_ctx_sync(ctx); for (auto *c : col) if (c) (void)ss_dev_free(ctx, c); }
@@ -941,11 +985,18 @@ int ssh_gl_prove_files_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t tr
                 ok(ss_running_product_gl64x3(ctx, rc, nullptr, rc + 2, nullptr, 4, n / 4, ch[2].data(), nullptr, ext.col, 4, 1, last_rc));
                 if (last_rc[0] != 1 || last_rc[1] || last_rc[2]) throw std::runtime_error("the range-check permutation does not close");
                 return std::vector<const uint64_t *>(ext.col, ext.col + 3);
-            }, prog_cb, user, proof_blob, proof_len);
+            }, prog_cb, check_cb, user, proof_blob, proof_len);
         if (ss_ctx_sync(ctx) != SS_OK) throw std::runtime_error(ss_last_error());
         if (times_out) { times_out[0] = gen_s; times_out[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int ssh_gl_prove_files_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len, uint64_t n_steps,
+                              const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint64_t *const d_cols[5], const uint32_t options[6],
+                              const uint8_t seed[32], const uint8_t statement_digest[32], const uint32_t *mask, uint32_t nmask, ssh_gl_program_cb prog_cb, void *user,
+                              double *times_out, uint64_t **proof_blob, uint64_t *proof_len) {
+    return ssh_gl_prove_files_device_checked(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols, options, seed,
+                                             statement_digest, mask, nmask, prog_cb, nullptr, user, times_out, proof_blob, proof_len);
 }
 
 static std::vector<Felt> felts_of_challenges(const uint64_t *challenges, uint32_t nchallenges) {

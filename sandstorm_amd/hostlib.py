@@ -592,12 +592,76 @@ def _gl_program_callback(ctx, air, n, tables, statement, keep):
     return GL_PROG_CB(prog_cb)
 
 
-def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, statement=None):
+GL_CHECK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64))
+
+
+def gl_check_blob(prog, domains, names, domain_names, d_tables=0, table_desc=()):
+    """the blob of ssh_gl_check_cb (host/gl_check_blob.hpp): header, code, constants, table descriptions, then per check its factor
+    lists and its two names (byte length + bytes packed eight to a word) -> uint64 array"""
+    def text(t):
+        b = t.encode()
+        return [len(b)] + [int.from_bytes(b[i:i + 8], "little") for i in range(0, len(b), 8)]
+    words = [len(prog.code) // 2, len(prog.consts), prog.n_slots, len(table_desc) // 2, int(d_tables), len(domains)]
+    words += [int(w) for w in prog.code] + [int(v) for c in prog.consts for v in c] + [int(v) for v in table_desc]
+    for (num, den), name, dname in zip(domains, names, domain_names):
+        for fs in (num, den):
+            words += [len(fs)] + [int(v) for f in fs for v in f]
+        words += text(name) + text(dname)
+    return np.array(words, dtype=np.uint64)
+
+
+def _gl_check_callback(air, n, statement, keep):
+    """ssh_gl_check_cb for a goldilocks.Air with a `checks` member; what it allocates stays in `keep`"""
+    if air.checks is None:
+        raise ValueError("the AIR '%s' has no check program" % air.name)
+
+    def check_cb(_user, ch_ptr, nch, blob_out, len_out):
+        try:
+            ch = [tuple(int(ch_ptr[3 * i + k]) for k in range(3)) for i in range(nch)]
+            blob = np.ascontiguousarray(gl_check_blob(*air.checks(n, ch, statement)))
+            keep.append(blob)
+            blob_out[0] = C.cast(blob.ctypes.data, C.POINTER(C.c_uint64))
+            len_out[0] = len(blob)
+            return 0
+        except Exception:
+            import traceback
+            traceback.print_exc()
+            return 1
+    return GL_CHECK_CB(check_cb)
+
+
+def gl_check_trace(ctx, air, cols, challenges, statement=None):
+    """goldilocks.check_trace by the C++ host (host_capi.cpp ssh_gl_check_trace -> gl::check_trace -> ss_check_constraints_gl64x3): the
+    check program comes from here through the callback, the report from there.  -> [(index, name, domain, first_row, count)]"""
+    n = int(cols[0].shape[0]) if hasattr(cols[0], "shape") else int(cols[0].nbytes // 8)
+    keep = []
+    cb = _gl_check_callback(air, n, statement, keep)
+    ch = np.ascontiguousarray([[int(v) for v in c] for c in challenges], dtype=np.uint64).reshape(-1)
+    fn = load().ssh_gl_check_trace
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, GL_CHECK_CB, C.c_void_p,
+                   C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
+    n_bad, report = C.c_uint32(), C.c_void_p()
+    _check(fn(ctx.handle, be._ptr_array(cols), len(cols), n.bit_length() - 1, ch.ctypes.data_as(C.POINTER(C.c_uint64)), len(challenges), cb, None,
+              C.byref(n_bad), C.byref(report)))
+    text = C.string_at(report.value).decode() if report.value else ""
+    load().ssh_free(report)
+    del keep[:]
+    out = []
+    for line in text.splitlines():
+        index, name, domain, first_row, count = line.split("\t")
+        out.append((int(index), name, domain, int(first_row), int(count)))
+    assert len(out) == n_bad.value
+    return out
+
+
+def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, statement=None, validate=False):
     """the 64-bit field's claim by the C++ host (host/goldilocks_prover.cpp ssh_gl_prove; the mirror of goldilocks.Prover.prove, which
     writes the same proof arrays): every stage a kernel behind the C ABI, the transcript in C++; what the LAYOUT decides comes from here
     through two callbacks - the extension trace's coordinate columns for the drawn challenges (build_extension, as goldilocks.Prover
     takes it) and the lowered composition program for them (air.composition + air_program.lower).  air: a goldilocks.Air; base_cols:
-    device columns of n values.  -> goldilocks.Proof"""
+    device columns of n values.  validate: the trace is checked against the AIR before the extension commitment (ssh_gl_prove_checked
+    with air.checks' program through a third callback); a trace that fails raises SandstormHipError with goldilocks.Prover's message.
+    -> goldilocks.Proof"""
     from . import goldilocks as gs
     opt = options or gs.Options()
     n = int(base_cols[0].shape[0]) if hasattr(base_cols[0], "shape") else int(base_cols[0].nbytes // 8)
@@ -620,12 +684,17 @@ def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, s
     h = load()
     h.ssh_gl_prove.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32),
                                C.c_uint32, C.c_uint32, C.c_uint32, GL_EXT_CB, GL_PROG_CB, C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    h.ssh_gl_prove_checked.argtypes = h.ssh_gl_prove.argtypes[:13] + [GL_CHECK_CB] + h.ssh_gl_prove.argtypes[13:]
     opts = (C.c_uint32 * 6)(opt.num_queries, opt.log_blowup, opt.grinding, opt.fold, opt.max_remainder, 1 if opt.hash == "sha256" else 0)
     mask = np.ascontiguousarray([v for cell in air.mask for v in cell], dtype=np.uint32)
     out, ln = C.POINTER(C.c_uint64)(), C.c_uint64()
-    _check(h.ssh_gl_prove(ctx.handle, opts, bytes(seed), gs.statement_digest(statement), be._ptr_array(base_cols), len(base_cols), n,
-                          mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask), air.num_challenges, air.num_ext, GL_EXT_CB(ext_cb), _gl_program_callback(ctx, air, n, tables, statement, keep), None,
-                          C.byref(out), C.byref(ln)))
+    head = (ctx.handle, opts, bytes(seed), gs.statement_digest(statement), be._ptr_array(base_cols), len(base_cols), n,
+            mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask), air.num_challenges, air.num_ext, GL_EXT_CB(ext_cb),
+            _gl_program_callback(ctx, air, n, tables, statement, keep))
+    if validate:
+        _check(h.ssh_gl_prove_checked(*head, _gl_check_callback(air, n, statement, keep), None, C.byref(out), C.byref(ln)))
+    else:
+        _check(h.ssh_gl_prove(*head, None, C.byref(out), C.byref(ln)))
     w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
     h.ssh_free(out)
     del keep[:]
@@ -708,10 +777,12 @@ def gl_trace_last_stats():
     return {"bytes_uploaded": int(out[0])}
 
 
-def gl_prove_files(ctx, air, options, seed, trace_bin: bytes, memory_bin: bytes, pi, dev_cols, tables=None):
+def gl_prove_files(ctx, air, options, seed, trace_bin: bytes, memory_bin: bytes, pi, dev_cols, tables=None, validate=False):
     """the 64-bit field's claim from the files in one call (host_capi.cpp ssh_gl_prove_files_device): the base columns made on the device
     in `dev_cols`, the extension column built by the C++ host, then gl_prove's proof; the composition program comes from here
-    (air.composition for the statement `pi`).  -> (goldilocks.Proof, {"trace_gen_s", "total_s"})"""
+    (air.composition for the statement `pi`).  validate: as for gl_prove (ssh_gl_prove_files_device_checked); what the files path refuses
+    without it - the files' errors, a range-check permutation that does not close - it refuses first and in the same words.
+    -> (goldilocks.Proof, {"trace_gen_s", "total_s"})"""
     from . import goldilocks as gs
     opt = options or gs.Options()
     if len(dev_cols) != 5:
@@ -726,8 +797,14 @@ def gl_prove_files(ctx, air, options, seed, trace_bin: bytes, memory_bin: bytes,
     opts = (C.c_uint32 * 6)(opt.num_queries, opt.log_blowup, opt.grinding, opt.fold, opt.max_remainder, 1 if opt.hash == "sha256" else 0)
     mask = np.ascontiguousarray([v for cell in air.mask for v in cell], dtype=np.uint32)
     out, ln, times = C.POINTER(C.c_uint64)(), C.c_uint64(), (C.c_double * 2)()
-    _check(fn(ctx.handle, *args, be._ptr_array(dev_cols), opts, bytes(seed), gs.statement_digest(pi), mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask),
-              _gl_program_callback(ctx, air, n, tables, pi, keep), None, times, C.byref(out), C.byref(ln)))
+    head = (ctx.handle, *args, be._ptr_array(dev_cols), opts, bytes(seed), gs.statement_digest(pi), mask.ctypes.data_as(C.POINTER(C.c_uint32)), len(air.mask),
+            _gl_program_callback(ctx, air, n, tables, pi, keep))
+    if validate:
+        fnc = load().ssh_gl_prove_files_device_checked
+        fnc.argtypes = fn.argtypes[:-5] + [GL_PROG_CB, GL_CHECK_CB] + fn.argtypes[-4:]
+        _check(fnc(*head, _gl_check_callback(air, n, pi, keep), None, times, C.byref(out), C.byref(ln)))
+    else:
+        _check(fn(*head, None, times, C.byref(out), C.byref(ln)))
     w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
     load().ssh_free(out)
     del keep[:], keep_args

@@ -321,6 +321,26 @@ def composition(n, hints: Hints, challenges, alpha, tables: Tables):
     return root
 
 
+CHECK_MAX_FACTORS = 16                               # SS_CHECK_MAX_FACTORS
+
+
+def check_program(n, hints: Hints, challenges):
+    """The trace check's program (ss_check_constraints_gl64x3): the bare numerators of the 47 constraints in the reference's order,
+    each left in accumulator 0 and followed by CHECK k - no composition coefficient, no zerofier multiplier, no table - with
+    sub-expressions shared across constraints.  -> (air_program.Program over Fq3, [(num, den)] zerofier factor lists (p, e) per
+    constraint, constraint names, domain names), all in constraints() order"""
+    cs = constraints(hints, challenges)
+    domains = []
+    for c in cs:
+        num, den = [tuple(f) for f in c.domain.num(n)], [tuple(f) for f in c.domain.den(n)]
+        if len(num) > CHECK_MAX_FACTORS or len(den) > CHECK_MAX_FACTORS:
+            raise ValueError("constraint %s: the domain '%s' has %d numerator and %d denominator factors, more than %d" %
+                             (c.name, c.domain.name, len(num), len(den), CHECK_MAX_FACTORS))
+        domains.append((num, den))
+    prog = ap.lower_checks([c.numerator for c in cs], P, ext=True)
+    return prog, domains, [c.name for c in cs], [c.domain.name for c in cs]
+
+
 def mask(constraint_list=None):
     """the (component column, row offset) cells the constraints read, sorted"""
     cells = set()
