@@ -79,6 +79,14 @@ def test_the_64_bit_field(emulated_library):
     assert "61 passed" in out, out[-500:]                     # 34 + 17 sizes + folds, row shapes (SHA-256's padding edges too), running products + 2 proofs + the C++ host's two
 
 
+def test_edge_words_of_the_64_bit_field(emulated_library):
+    """tests/test_gpu_gl64_edge_values.py: the 64-bit field's kernels on the words at both ends of the field and at its 32-bit seams,
+    and on outputs forced onto residues below 2^32 - 1 - where a lazy word (csrc/gl64.h) that reaches HBM, a hash or a comparison
+    shows with certainty; uniform draws reach those words once in 2^32"""
+    out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_gl64_edge_values.py"])
+    assert "58 passed" in out, out[-500:]                     # 9 transforms + 16 folds + 6 out-of-domain + 6 DEEP + 6 programs + 2 checks + 10 products + 3 row shapes
+
+
 def test_extension_columns_and_compiled_constraint_kernels(emulated_library):
     """tests/test_gpu_extension.py (the scans behind Trace::build_extension_columns) and tests/test_gpu_real_quotient.py (the generated
     starknet / recursive kernels against the interpreter and the oracle over whole domains)"""
