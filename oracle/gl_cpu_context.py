@@ -2,7 +2,7 @@
 64-bit field: the SAME prover code that sequences the HIP kernels then runs on the CPU (torch CPU tensors for its buffers), so a
 whole proof can be compared with a GPU-made one array for array (tests/test_goldilocks_stark.py) - a pin of the pipeline, not of
 one kernel.  Every stage is a definition-level restatement: oracle/goldilocks.c (transforms, constraint program, out-of-domain
-evaluation, DEEP term by term, FRI fold), hashlib (Blake2s rows and tree), Python integers (running products, proof of work).
+evaluation, DEEP term by term, FRI fold), hashlib (Blake2s or SHA-256 rows and tree), Python integers (running products, proof of work).
 Nothing under sandstorm_amd/ imports this module."""
 import hashlib
 
@@ -58,6 +58,17 @@ def _bitrev_perm(n):
     return np.array([int(format(i, "0%db" % bits)[::-1], 2) if bits else 0 for i in range(n)])
 
 
+HASH_BLAKE2S, HASH_SHA256 = 2, 4            # SS_HASH_* / SS_TREE_* of include/sandstorm_hip.h: what goldilocks.Prover passes
+TREE_BLAKE2S, TREE_SHA256 = 3, 4
+
+
+def _hash_of(kind, names):
+    """the hashlib function of a row-hash or tree kind of the 64-bit field's claims (Blake2s-256, or SHA-256 for Options(hash="sha256"))"""
+    if kind not in names:
+        raise ValueError("the 64-bit field's oracle context has no hash of kind %r" % (kind,))
+    return names[kind]
+
+
 class GlCpuContext:
     def __init__(self):
         self.handle = None
@@ -94,16 +105,18 @@ class GlCpuContext:
 
     def hash_rows_gl64(self, segments, seg_len, nrows, out, hash_kind=None):
         segs = self._segments(segments, seg_len, nrows)
+        h = _hash_of(hash_kind, {None: hashlib.blake2s, HASH_BLAKE2S: hashlib.blake2s, HASH_SHA256: hashlib.sha256})
         o = out.numpy()
         for i in range(nrows):
             row = b"".join(int(s[i * seg_len + e]).to_bytes(8, "little") for s in segs for e in range(seg_len))
-            o[i] = np.frombuffer(hashlib.blake2s(row).digest(), dtype=np.uint8)
+            o[i] = np.frombuffer(h(row).digest(), dtype=np.uint8)
 
     def merkle_build(self, tree, n_friendly, leaf_kind, leaves, n, nodes, tags=None, leaf_order=NATURAL):
+        h = _hash_of(tree, {TREE_BLAKE2S: hashlib.blake2s, TREE_SHA256: hashlib.sha256})
         nd = nodes.numpy()
         nd[n:2 * n] = leaves.numpy()
         for k in range(n - 1, 0, -1):
-            nd[k] = np.frombuffer(hashlib.blake2s(bytes(nd[2 * k]) + bytes(nd[2 * k + 1])).digest(), dtype=np.uint8)
+            nd[k] = np.frombuffer(h(bytes(nd[2 * k]) + bytes(nd[2 * k + 1])).digest(), dtype=np.uint8)
         nd[0] = 0
         return bytes(nd[1]), 0
 

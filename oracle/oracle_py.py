@@ -205,6 +205,8 @@ def merkle_build(tree, n_friendly, leaf_kind, leaves):
     """leaves: (n,32) uint8 digests or (n,4) uint64 felts -> (nodes (2n,32) u8, tags (2n,) u8)."""
     lv = np.ascontiguousarray(leaves)
     n = lv.shape[0]
+    if n < 2:                               # as the ABI refuses them (ss_merkle_build); the C code below would write outside its arrays
+        raise ValueError("a Merkle tree needs at least two leaves (got %d)" % n)
     nodes = np.zeros((2 * n, 32), dtype=np.uint8)
     tags = np.zeros(2 * n, dtype=np.uint8)
     lib().or_merkle_build(C.c_int(tree), C.c_uint(n_friendly), C.c_int(leaf_kind), _ptr(lv),

@@ -166,6 +166,24 @@ def fri_shape(n_lde, opt: Options):
     return layers, length
 
 
+def fri_geometry(n_lde, opt: Options):
+    """fri_shape for the provers, asked before anything is uploaded or launched: the option ranges the verifier insists on (_verify:
+    folding factor 2, 4, 8 or 16; max remainder 1 .. 2^16) and this field's own stopping rule (a layer is the remainder once its length
+    is <= max_remainder * blowup; every layer above it a multiple of the folding factor).  -> (layers, remainder length), or a
+    ValueError naming the rule and the numbers - without it a bad geometry is refused only at step 7, after every commitment."""
+    nums = "(LDE domain %r, folding factor %r, max remainder %r, log blowup %r)" % (n_lde, opt.fold, opt.max_remainder, opt.log_blowup)
+    if any(not isinstance(v, (int, np.integer)) or isinstance(v, bool) for v in (n_lde, opt.fold, opt.max_remainder, opt.log_blowup)):
+        raise ValueError("FRI geometry refused: the options are not integers " + nums)
+    if opt.fold not in (2, 4, 8, 16):
+        raise ValueError("FRI geometry refused: the FRI folding factor must be 2, 4, 8 or 16 " + nums)
+    if not 1 <= opt.max_remainder <= 1 << 16:
+        raise ValueError("FRI geometry refused: the max remainder must be 1 .. 65536 " + nums)
+    try:
+        return fri_shape(int(n_lde), opt)
+    except ValueError as e:
+        raise ValueError("FRI geometry refused: %s %s" % (e, nums))
+
+
 def _powers3(a, count):
     out, cur = [], (1, 0, 0)
     for _ in range(count):
@@ -241,6 +259,7 @@ class Prover:
         if lb != 1:
             raise ValueError("the composition split (even / odd coefficients) is written for blowup 2")
         N = n << lb
+        fri_geometry(N, opt)                        # refused here, not at step 7 after every commitment
         dev = base_cols[0].device
         new = lambda rows, width=None: torch.empty((rows,) if width is None else (rows, width), dtype=torch.int64, device=dev)   # fully written below
         coin = Coin(transcript_seed(seed, opt, n, statement), opt.hash)

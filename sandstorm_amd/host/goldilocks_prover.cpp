@@ -179,6 +179,21 @@ std::string describe_failures(const std::vector<ConstraintFailure> &f) {
            (a.count == 1 ? " row" : " rows");
 }
 
+FriShape fri_shape(const Options &opt, uint64_t n_lde) {
+    const std::string nums = " (LDE domain " + std::to_string(n_lde) + ", folding factor " + std::to_string(opt.fold) + ", max remainder " +
+                             std::to_string(opt.max_remainder) + ", log blowup " + std::to_string(opt.log_blowup) + ")";
+    if (opt.fold != 2 && opt.fold != 4 && opt.fold != 8 && opt.fold != 16)
+        throw std::runtime_error("FRI geometry refused: the FRI folding factor must be 2, 4, 8 or 16" + nums);
+    if (opt.max_remainder < 1 || opt.max_remainder > (1u << 16)) throw std::runtime_error("FRI geometry refused: the max remainder must be 1 .. 65536" + nums);
+    if (opt.log_blowup > 4) throw std::runtime_error("FRI geometry refused: the log blowup must be at most 4" + nums);
+    FriShape s{0, n_lde};
+    for (; s.last_len > ((uint64_t)opt.max_remainder << opt.log_blowup); s.last_len /= opt.fold) {
+        if (s.last_len % opt.fold) throw std::runtime_error("FRI geometry refused: a FRI layer's length is not a multiple of the folding factor" + nums);
+        ++s.layers;
+    }
+    return s;
+}
+
 Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &statement_digest, const std::vector<const uint64_t *> &base_cols,
             uint64_t n, const std::vector<std::pair<uint32_t, uint32_t>> &mask, uint32_t num_challenges, uint32_t num_ext,
             const ExtensionBuilder &build_extension, const ProgramBuilder &build_program, const CheckBuilder &build_check) {
@@ -188,6 +203,7 @@ Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &s
     while ((1ull << log_n) < n) ++log_n;
     const uint32_t lb = opt.log_blowup;
     const uint64_t N = n << lb, OFFSET = 7;
+    const uint32_t n_layers = fri_shape(opt, N).layers;     // refused here, not at step 7 after every commitment
     const int row_hash = opt.sha256 ? SS_HASH_SHA256 : SS_HASH_BLAKE2S, tree = opt.sha256 ? SS_TREE_SHA256 : SS_TREE_BLAKE2S;
     Coin coin(transcript_seed(seed, opt, n, statement_digest), opt.sha256);
     Proof proof;
@@ -321,11 +337,6 @@ Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &s
     ok(ss_deep_compose_gl64x3(ctx, trace_ev.data(), (uint32_t)trace_ev.size(), comp_ev.data(), 6, log_n, lb, OFFSET, mc.data(), mo.data(), (uint32_t)mask.size(),
                               proof.ood_trace.data(), coefs.data(), proof.ood_comp.data(), coefs.data() + 3 * mask.size(), z.data(), zc.data(), layer->u64()));
     // 7. FRI
-    uint32_t n_layers = 0;
-    for (uint64_t len = N; len > ((uint64_t)opt.max_remainder << lb); len /= opt.fold) {
-        if (len % opt.fold) throw std::runtime_error("a FRI layer's length is not a multiple of the folding factor");
-        ++n_layers;
-    }
     uint32_t log_fold = 0;
     while ((1u << log_fold) < opt.fold) ++log_fold;
     struct Layer { DevP evals; Commitment com; uint64_t rows; std::vector<const uint64_t *> segs; };

@@ -23,6 +23,12 @@ struct Options {                                            // goldilocks.py Opt
     uint32_t num_queries = 65, log_blowup = 1, grinding = 16, fold = 8, max_remainder = 16;
     bool sha256 = false;                                    // the parts cli/src/main.rs:119-120 names: SHA-256 trees and a SHA-256 coin
 };
+// The FRI layers over an LDE domain of n_lde points, asked before anything is uploaded or launched (goldilocks.py fri_geometry): the
+// verifier's option ranges (folding factor 2, 4, 8 or 16; max remainder 1 .. 2^16) and this field's own stopping rule - a layer is the
+// remainder once its length is <= max_remainder << log_blowup, every layer above it a multiple of the folding factor.  Throws, naming
+// the rule and the numbers.
+struct FriShape { uint32_t layers; uint64_t last_len; };
+FriShape fri_shape(const Options &opt, uint64_t n_lde);
 struct Opening {
     uint32_t width = 0, depth = 0;
     std::vector<uint64_t> rows;                             // [positions][width]

@@ -67,6 +67,8 @@ static int prove_impl(ss_ctx *ctx, ssh_air *air_h, int tree_kind, uint32_t n_fri
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
         lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
+        if (log_n > 40) throw std::runtime_error("a trace of 2^" + std::to_string(log_n) + " rows");
+        fri_geometry(opt, 1ull << log_n);   // and a FRI geometry the verifiers refuse (prover.hpp)
         Matrix base;
         base.nrows = 1ull << log_n;
         for (uint32_t c = 0; c < nbase; ++c) base.cols.push_back(d_base[c]);
@@ -118,6 +120,31 @@ int ssh_prove_wire_with_nonce(ss_ctx *ctx, ssh_air *air_h, int tree_kind, uint32
                       proof_bytes, proof_len, &pow_nonce);
 }
 void ssh_free(void *p) { free(p); }
+
+// The provers' FRI rules as calls of their own, host arithmetic only (no context, no device): what every prove entry point of this file
+// asks before it uploads or launches anything.  -> 0 with the layer count and the remainder's length, or 1 with the rule's message in
+// ssh_last_error.  ssh_fri_geometry: the 252-bit path (prover.hpp fri_geometry; out = remainder coefficients).  ssh_gl_fri_geometry:
+// the 64-bit field (goldilocks_prover.hpp fri_shape; out = length of the last layer, which is the remainder).
+int ssh_fri_geometry(uint64_t trace_len, uint32_t fold, uint32_t max_remainder, uint32_t *layers, uint64_t *remainder_len) {
+    try {
+        ProofOptions opt;
+        opt.fri_folding_factor = fold; opt.fri_max_remainder_coeffs = max_remainder;
+        const FriGeometry g = fri_geometry(opt, trace_len);
+        if (layers) *layers = g.layers;
+        if (remainder_len) *remainder_len = g.remainder_len;
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int ssh_gl_fri_geometry(uint64_t n_lde, uint32_t log_blowup, uint32_t fold, uint32_t max_remainder, uint32_t *layers, uint64_t *last_len) {
+    try {
+        gl::Options opt;
+        opt.log_blowup = log_blowup; opt.fold = fold; opt.max_remainder = max_remainder;
+        const gl::FriShape s = gl::fri_shape(opt, n_lde);
+        if (layers) *layers = s.layers;
+        if (last_len) *last_len = s.last_len;
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
 
 // ---- one proof over several ranks (sharded.hpp).  Every rank calls ssh_prove_sharded with its own context and AIR handle; the
 // proof (reference wire format) comes out on rank 0.  Transport: a local group (ranks = threads of this process:
@@ -189,6 +216,8 @@ static int prove_sharded_impl(ss_ctx *ctx, ssh_air *air_h, int tree_kind, uint32
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
         lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
+        if (log_n > 40) throw std::runtime_error("a trace of 2^" + std::to_string(log_n) + " rows");
+        fri_geometry(opt, 1ull << log_n);   // and a FRI geometry the verifiers refuse (prover.hpp)
         std::unique_ptr<Transport> local = lg ? make_local_transport(*lg, rank) : nullptr;
         Transport *comm = lg ? local.get() : reinterpret_cast<Transport *>(rccl);
         if (comm->world != world || comm->rank != rank) throw std::runtime_error("ssh_prove_sharded: the group has another number of ranks, or this is another rank of it");
@@ -544,6 +573,7 @@ int ssh_prove_files(ss_ctx *ctx, int layout, const uint8_t *trace_bin, uint64_t 
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
         lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before anything is uploaded or launched
+        fri_geometry(opt, job.n);     // and a FRI geometry the verifiers refuse (prover.hpp)
         std::mutex m;
         std::condition_variable cv;
         std::vector<uint64_t> ticket(job.ncols, 0);
@@ -671,6 +701,7 @@ int ssh_prove_files_device(ss_ctx *ctx, int layout, const uint8_t *trace_bin, ui
             opt.fri_folding_factor = options[3]; opt.fri_max_remainder_coeffs = options[4];
         }
         lde_log_blowup(opt);          // 2, 4, 8 or 16: refused here, before the files go up and the generator writes d_cols
+        fri_geometry(opt, job.n);     // and a FRI geometry the verifiers refuse (prover.hpp)
         job.run_device(ctx, d_cols);
         const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         Matrix base;
@@ -749,6 +780,7 @@ int ssh_prove_files_sharded_device(ss_ctx *ctx, int layout, const uint8_t *trace
         const TraceJob job = make_trace_job(layout, trace_bin, trace_len, memory_bin, memory_len, rc_min, rc_max, n_steps, segments, mem_addresses, mem_values,
                                             n_mem, instances, counts);
         const ClaimArgs ca = unpack_claim(air_h, tree_kind, n_friendly_layers, coin_kind, seed, options);
+        fri_geometry(ca.opt, job.n);     // a FRI geometry the verifiers refuse (prover.hpp): before anything is uploaded or launched
         if (ca.claim.air->num_base_columns != job.ncols) throw std::runtime_error("ssh_prove_files_sharded_device: the AIR is another layout's");
         if (job.n % world) throw std::runtime_error("ssh_prove_files_sharded_device: the trace's rows do not divide over the ranks");
         // everything below lives in the context's pool and goes back to it on every way out (the buffers are RAII), after what this
@@ -966,6 +998,12 @@ int ssh_gl_prove_files_device_checked(ss_ctx *ctx, const uint8_t *trace_bin, uin
     try {
         if (!ctx || !options || !seed || !statement_digest || !d_cols || !mask || !prog_cb || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove_files_device: NULL argument");
         const auto t_start = std::chrono::steady_clock::now();
+        {                                                            // a FRI geometry gl::prove would refuse: before the files go up
+            gl::Options opt;
+            opt.log_blowup = options[1]; opt.fold = options[3]; opt.max_remainder = options[4];
+            // (a cycle count or a blowup that is refused anyway keeps the message it has: the trace plan's, gl::prove's)
+            if (opt.log_blowup == 1 && n_steps && !(n_steps & (n_steps - 1)) && n_steps <= (1ull << 28)) gl::fri_shape(opt, (16 * n_steps) << opt.log_blowup);
+        }
         plain_base_trace_device(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols);
         const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         const uint64_t n = 16 * n_steps;

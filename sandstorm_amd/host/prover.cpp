@@ -27,6 +27,26 @@ uint32_t lde_log_blowup(const ProofOptions &opt) {
     return log2u(f);
 }
 
+FriGeometry fri_geometry(const ProofOptions &opt, uint64_t trace_len) {
+    const uint64_t fold = opt.fri_folding_factor, max_remainder = opt.fri_max_remainder_coeffs;
+    const std::string nums = " (trace length " + std::to_string(trace_len) + ", folding factor " + std::to_string(fold) +
+                             ", max remainder coefficients " + std::to_string(max_remainder) + ")";
+    if (fold != 2 && fold != 4 && fold != 8 && fold != 16)
+        throw std::runtime_error("FRI geometry refused: the FRI folding factor must be 2, 4, 8 or 16" + nums);
+    if (max_remainder < 1 || (max_remainder & (max_remainder - 1)))
+        throw std::runtime_error("FRI geometry refused: the FRI max remainder is not a power of two >= 1" + nums);
+    if (trace_len < 1 || (trace_len & (trace_len - 1)))
+        throw std::runtime_error("FRI geometry refused: the trace length is not a power of two" + nums);
+    FriGeometry g{0, trace_len};
+    while (g.remainder_len > max_remainder) {
+        if (g.remainder_len % fold)
+            throw std::runtime_error("FRI geometry refused: the trace length is not the remainder bound times a power of the folding factor" + nums);
+        g.remainder_len /= fold;
+        ++g.layers;
+    }
+    return g;
+}
+
 // ------------------------------------------------------------------ device objects
 DeviceBuffer::DeviceBuffer(ss_ctx *ctx, size_t bytes) : ctx_(ctx), bytes_(bytes) { ok(ss_dev_alloc(ctx, bytes, &ptr_)); }
 DeviceBuffer::~DeviceBuffer() { if (ptr_) ss_dev_free(ctx_, ptr_); }
@@ -224,6 +244,7 @@ Proof Prover::prove(const Digest &coin_seed, const Matrix &base_trace, const Ext
     Air &air = *claim_.air;
     const uint64_t n = base_trace.nrows;
     const uint32_t lb = lde_log_blowup(opt_), log_n = log2u(n), log_N = log_n + lb;
+    fri_geometry(opt_, n);              // refused here, before anything is launched
     const uint64_t N = n << lb;
     const uint32_t ncomp = conv_.composition_columns;
     if (ncomp != 2) throw std::runtime_error("composition split implemented for two composition columns");

@@ -29,6 +29,14 @@ struct ProofOptions {                   // cli/src/main.rs:51-60 defaults
 // throws for any other value, naming the set
 uint32_t lde_log_blowup(const ProofOptions &opt);
 
+// The FRI layers of a proof over `trace_len` rows, by the verifiers' own rule (verifier.cpp; verifier.py fri_layer_count): the folding
+// factor is 2, 4, 8 or 16, the max remainder a power of two >= 1, and the trace length the remainder bound times a power of the folding
+// factor.  The layers then fit into any LDE domain (fold^layers divides the trace length; the last layer keeps blowup * remainder >= 2
+// rows).  Anything else throws, naming the rule and the three numbers: the provers call this before they upload or launch anything - a
+// geometry the verifiers refuse otherwise ends in a one-row Merkle tree or a layer length below zero, after every commitment.
+struct FriGeometry { uint32_t layers; uint64_t remainder_len; };
+FriGeometry fri_geometry(const ProofOptions &opt, uint64_t trace_len);
+
 struct Conventions {                    // ministark-internal, SURVEY.md Appendix A
     uint64_t lde_offset = 3;            // M2
     uint32_t composition_columns = 2;   // M5

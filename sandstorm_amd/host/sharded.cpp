@@ -564,6 +564,7 @@ bool ShardedProver::prove(const Digest &coin_seed, const std::map<uint32_t, uint
     const uint32_t R = comm_.world, r = comm_.rank;
     if (R & (R - 1)) throw std::runtime_error("the row blocks need a power-of-two number of ranks");
     const uint32_t lb = lde_log_blowup(opt_), log_n = log2u(n), log_N = log_n + lb;
+    fri_geometry(opt_, n);                       // refused on every rank alike, before anything is launched or exchanged
     const uint64_t N = n << lb, B = N / R;
     if (N % R || n / R < 1) throw std::runtime_error("more ranks than trace rows");
     const uint32_t ncomp = conv_.composition_columns;

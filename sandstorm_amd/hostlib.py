@@ -90,6 +90,8 @@ def load():
         h.ssh_air_set_validation.argtypes = [C.c_void_p, C.c_int]
         h.ssh_check_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
+        h.ssh_fri_geometry.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        h.ssh_gl_fri_geometry.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         _host = h
     return _host
 
@@ -97,6 +99,23 @@ def load():
 def _check(rc):
     if rc != 0:
         raise _lib.SandstormHipError("host: " + load().ssh_last_error().decode())
+
+
+def fri_geometry(trace_len, fold, max_remainder):
+    """the C++ provers' FRI rule on the 252-bit path (host/prover.cpp fri_geometry; prover.fri_geometry is its mirror), host arithmetic
+    only: -> (layers, remainder coefficients), or SandstormHipError with the rule's message.  The arguments are the C call's: a trace
+    length below 2^64, options below 2^32"""
+    layers, rem = C.c_uint32(), C.c_uint64()
+    _check(load().ssh_fri_geometry(trace_len, fold, max_remainder, C.byref(layers), C.byref(rem)))
+    return layers.value, rem.value
+
+
+def gl_fri_geometry(n_lde, log_blowup, fold, max_remainder):
+    """the same for the 64-bit field (host/goldilocks_prover.cpp fri_shape; goldilocks.fri_geometry): -> (layers, length of the last
+    layer, which is the remainder)"""
+    layers, last = C.c_uint32(), C.c_uint64()
+    _check(load().ssh_gl_fri_geometry(n_lde, log_blowup, fold, max_remainder, C.byref(layers), C.byref(last)))
+    return layers.value, last.value
 
 
 _AIR_FACTORIES = {}

@@ -140,6 +140,33 @@ def lde_log_blowup(options):
     return _log2(options.lde_blowup_factor)
 
 
+def fri_geometry(trace_len, fold, max_remainder):
+    """-> (number of FRI layers, number of remainder coefficients) for a trace of `trace_len` rows, by the verifiers' own rule
+    (verifier.fri_layer_count; host/prover.cpp fri_geometry is the same rule): the folding factor is 2, 4, 8 or 16, the max remainder
+    a power of two >= 1, and the trace length the remainder bound times a power of the folding factor.  The layers then fit into any
+    LDE domain: fold^layers divides the trace length, and the last layer still has blowup * remainder >= 2 rows.  Anything else is a
+    ValueError naming the rule and the three numbers - the provers call this before they upload or launch anything, since a geometry
+    the verifiers refuse otherwise ends in a one-row Merkle tree or a negative layer length after every commitment."""
+    nums = "(trace length %r, folding factor %r, max remainder coefficients %r)" % (trace_len, fold, max_remainder)
+    for v in (trace_len, fold, max_remainder):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError("FRI geometry refused: the options are not integers " + nums)
+    trace_len, fold, max_remainder = int(trace_len), int(fold), int(max_remainder)
+    if fold not in (2, 4, 8, 16):
+        raise ValueError("FRI geometry refused: the FRI folding factor must be 2, 4, 8 or 16 " + nums)
+    if max_remainder < 1 or max_remainder & (max_remainder - 1):
+        raise ValueError("FRI geometry refused: the FRI max remainder is not a power of two >= 1 " + nums)
+    if trace_len < 1 or trace_len & (trace_len - 1):
+        raise ValueError("FRI geometry refused: the trace length is not a power of two " + nums)
+    degree_bound, layers = trace_len, 0
+    while degree_bound > max_remainder:
+        if degree_bound % fold:
+            raise ValueError("FRI geometry refused: the trace length is not the remainder bound times a power of the folding factor " + nums)
+        degree_bound //= fold
+        layers += 1
+    return layers, max(1, degree_bound)
+
+
 def _pow_limbs(base_limbs, count):
     """[alpha^0 .. alpha^(count-1)] as Montgomery limbs (tiny host arithmetic on transcript values)"""
     a = canonical(base_limbs)
@@ -166,6 +193,7 @@ class Prover:
         Tree = self.claim.tree
         n = base_trace.nrows
         lb = lde_log_blowup(opt)
+        fri_geometry(n, opt.fri_folding_factor, opt.fri_max_remainder_coeffs)     # refused here, before anything is uploaded or launched
         log_n = _log2(n)
         log_N, N = log_n + lb, n << lb
         ncomp = conv.composition_columns

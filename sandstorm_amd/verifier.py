@@ -196,6 +196,7 @@ def conjectured_security_bits(options, trace_len, tree_kind, coin_kind):
 def fri_layer_count(trace_len, fold, max_remainder):
     """number of FRI layers and the remainder's coefficient bound, as the provers compute them (prover.py step 8);
     the options are untrusted here: anything the provers would refuse is a rejection"""
+    _require(fold in (2, 4, 8, 16), "bad FRI folding factor")
     _require(max_remainder >= 1 and max_remainder & (max_remainder - 1) == 0, "FRI max remainder is not a power of two >= 1")
     degree_bound, nlayers = trace_len, 0
     while degree_bound > max_remainder:

@@ -152,6 +152,23 @@ def test_cpp_sharded_prover_over_ranks_as_threads(emulated_library):
     assert "14 passed" in out, out[-500:]                     # 7 mini + 2 friendly + 4 real AIR (2 with the extension trace as row blocks) + the too-few-rows error
 
 
+def test_fri_folding_factors_through_every_prover(emulated_library):
+    """tests/test_gpu_fri_options.py: proofs at folding factors 2, 4 and 16 by the Python and the C++ host on one device, by the sharded
+    prover (layers spread over the ranks, and a folding factor below the number of ranks) and by both hosts of the 64-bit field, each
+    the bytes of the same host code over the CPU oracle; FRI rows of 2, 4 and 16 Fq3 values against hashlib; and the geometries the
+    verifiers refuse, refused by every prover before its first launch"""
+    heavy()
+    ranks_as_threads = "sharded_prover or no_prover_launches"
+    out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_fri_options.py", "-k", "not (%s)" % ranks_as_threads])
+    assert "14 passed" in out, out[-500:]                     # 7 proofs by both hosts + 4 of the 64-bit field + 3 row shapes
+    os.environ["HIPEMU_THREADS"] = "1"           # the emulator's worker pool serves one launching thread: the ranks are the parallelism
+    try:
+        out = run_gpu_tests_on_host(emulated_library, ["tests/test_gpu_fri_options.py", "-k", ranks_as_threads])
+    finally:
+        del os.environ["HIPEMU_THREADS"]
+    assert "8 passed" in out, out[-500:]                      # 6 sharded proofs + the two refused geometries
+
+
 def test_cpp_sharded_prover_over_ranks_as_processes(emulated_library):
     """tests/hipemu/extra_sharded_host_procs.py: the same driver with the ranks as 2, 4 and 8 PROCESSES under torch.distributed.run - what
     `bench.py --gpus N` starts -, every process with its own emulated device, coin and columns, meeting in the driver's
