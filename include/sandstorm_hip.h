@@ -288,6 +288,13 @@ typedef struct ss_air_program {
  * length 2^log_N instead of a per-point field inversion. */
 ss_status ss_inverse_table(ss_ctx *ctx, uint32_t log_N, const uint64_t offset[4], const uint64_t c[4],
                            uint64_t *d_out);
+/* Copies of tables, each times a factor of its own, one after the other: with dst_j = len[0] + .. + len[j - 1],
+ * d_out[dst_j + k] = d_tables[first[j] + k] * factors[j] for k < len[j] (first, len in felts; factors: n_copies interchange
+ * images, host memory like first and len).  It is the launch ss_eval_quotient's compiled kernels queue in front of their parts -
+ * the multiplier-only periodic tables times 2^24, and times each constraint's coefficient (csrc/quotient_derive.h) - as a call
+ * of its own, for tests.  Every entry comes out fully reduced. */
+ss_status ss_table_copies(ss_ctx *ctx, const uint64_t *d_tables, const uint32_t *first, const uint32_t *len,
+                          const uint64_t *factors, uint32_t n_copies, uint64_t *d_out);
 ss_status ss_eval_quotient(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_lde_cols,
                            uint32_t ncols, uint32_t log_n, uint32_t log_blowup,
                            const uint64_t offset[4], uint64_t *d_out);

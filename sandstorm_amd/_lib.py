@@ -139,6 +139,7 @@ SIGNATURES = {
                                                C.c_void_p]),
     "ss_trace_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ss_inverse_table": (C.c_int, [C.c_void_p, C.c_uint32, _u64p, _u64p, C.c_void_p]),
+    "ss_table_copies": (C.c_int, [C.c_void_p, C.c_void_p, _u32p, _u32p, _u64p, C.c_uint32, C.c_void_p]),
     "ss_eval_quotient": (C.c_int, [C.c_void_p, C.POINTER(AirProgram), _vpp, C.c_uint32, C.c_uint32,
                                    C.c_uint32, _u64p, C.c_void_p]),
     "ss_eval_quotient_rows": (C.c_int, [C.c_void_p, C.POINTER(AirProgram), _vpp, C.c_uint32, C.c_uint32,

@@ -409,6 +409,15 @@ class Context:
         _k2, cp = _felt_ptr(c)
         check(self.lib.ss_inverse_table(self.handle, log_N, op, cp, _ptr_of(out)))
 
+    def table_copies(self, tables, first, lengths, factors, out):
+        """ss_table_copies: out = the tables [first[j], first[j] + lengths[j]) of `tables`, each times factors[j] (n x 4 u64, interchange
+        images), one after the other"""
+        n = len(first)
+        fa = (C.c_uint32 * n)(*[int(v) for v in first])
+        la = (C.c_uint32 * n)(*[int(v) for v in lengths])
+        fac = np.ascontiguousarray(factors, dtype=np.uint64).reshape(n, 4)
+        check(self.lib.ss_table_copies(self.handle, _ptr_of(tables), fa, la, fac.ctypes.data_as(C.POINTER(C.c_uint64)), n, _ptr_of(out)))
+
     def eval_quotient(self, program, tables, table_desc, lde_cols, log_n, log_blowup, offset, out):
         """program: air_program.Program; tables: device buffer of concatenated felts (or None);
         table_desc: flat [offset, log_len, ...] list"""

@@ -2425,6 +2425,32 @@ ss_status ss_inverse_table(ss_ctx *ctx, uint32_t log_N, const uint64_t offset[4]
     return SS_OK;
 }
 
+ss_status ss_table_copies(ss_ctx *ctx, const uint64_t *d_tables, const uint32_t *first, const uint32_t *len, const uint64_t *factors,
+                          uint32_t n_copies, uint64_t *d_out) {
+    if (!ctx || !d_tables || !first || !len || !factors || !d_out) return fail(SS_ERR_INVALID, "NULL argument");
+    if (n_copies == 0 || n_copies > (uint32_t)(QG_MAX_SCALED + QG_MAX_ALPHA)) return fail(SS_ERR_INVALID, "%u copies", n_copies);
+    std::vector<uint32_t> host(16 * (size_t)n_copies, 0u);
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < n_copies; ++j) {
+        if (len[j] == 0 || total + len[j] > 0xffffffffull) return fail(SS_ERR_INVALID, "copy %u: %u entries", j, len[j]);
+        uint32_t *c = &host[16 * (size_t)j];
+        c[0] = first[j]; c[1] = (uint32_t)total; c[2] = len[j];
+        const Fp f = fp_from_limbs64(factors + 4 * (size_t)j);
+        for (int k = 0; k < 8; ++k) c[8 + k] = f.v[k];
+        total += len[j];
+    }
+    ss_status st = ctx->ensure_scratch(host.size() * 4 + 256);
+    if (st != SS_OK) return st;
+    void *pinned = nullptr;
+    if ((st = ctx->stage_acquire(host.size() * 4, &pinned)) != SS_OK) return st;
+    memcpy(pinned, host.data(), host.size() * 4);
+    HIP_TRY(hipMemcpyAsync(ctx->scratch, pinned, host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->stage_event, ctx->stream));
+    HIP_TRY(launch_qg_copy_tables(ctx->stream, (const Fp *)d_tables, (Fp *)d_out, (const QgCopy *)ctx->scratch, n_copies, total));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SS_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2460,10 +2486,14 @@ ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_ai
     const uint64_t N = npoints;
     // constants in limb form: 9 x 28-bit limbs of the interchange image (add / sub / mov) and of the R280 form (fl_mul_r280)
     const uint32_t nc = prog->n_consts ? prog->n_consts : 1u;
-    // [constants | table descriptors, then those of the scaled copies | one step w^(lanes of the grid) per part, 32-byte aligned]
+    // [constants | table descriptors, then those of the scaled copies, then those of the alpha copies | one step w^(lanes of the grid)
+    //  per part, 32-byte aligned | what the copy kernel reads: one QgCopy per scaled table and per alpha copy]
     const size_t n_desc = (size_t)(prog->n_tables ? prog->n_tables : 1u) + gen.n_scaled;
-    const size_t wstep_at = (((size_t)nc * QG_CONST_STRIDE + 2 * n_desc) + 7) / 8 * 8;
-    std::vector<uint32_t> host(wstep_at + 8 * (size_t)QG_MAX_PARTS, 0u);
+    const size_t n_copies = (size_t)gen.n_scaled + gen.n_alpha;
+    const size_t wstep_at = (((size_t)nc * QG_CONST_STRIDE + 2 * (n_desc + gen.n_alpha)) + 7) / 8 * 8;
+    const size_t copies_at = wstep_at + 8 * (size_t)QG_MAX_PARTS;
+    static_assert(sizeof(QgCopy) == 64, "QgCopy is sixteen words of the staged block");
+    std::vector<uint32_t> host(copies_at + 16 * n_copies, 0u);
     for (uint32_t k = 0; k < prog->n_consts; ++k) {
         const Fp c = fp_from_limbs64(prog->consts + 4 * (size_t)k);
         Fp two24 = fp_zero(); two24.v[0] = 1u << 24;
@@ -2479,20 +2509,38 @@ ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_ai
         tdesc[2 * t] = prog->table_desc[2 * t];
         tdesc[2 * t + 1] = (uint32_t)((1ull << prog->table_desc[2 * t + 1]) - 1ull);
     }
-    // the multiplier-only tables times 2^24, one after the other behind the staged words (quotient_gen.h QG_TABLE_SCALED_RAW)
-    QgScaleArgs sc;
+    // the multiplier-only tables times 2^24, one after the other behind the staged words (quotient_gen.h QG_TABLE_SCALED_RAW), and
+    // behind them the alpha copies (QG_TABLE_ALPHA_RAW): table x the program's constant in the form the kernels expect, the factor made
+    // here from this call's constant table - the composition coefficient changes from proof to proof, nothing is cached
     uint64_t scaled_felts = 0;
     if (gen.n_scaled > (uint32_t)QG_MAX_SCALED) return fail(SS_ERR_UNSUPPORTED, "%u scaled tables > %d", gen.n_scaled, QG_MAX_SCALED);
-    for (uint32_t j = 0; j < gen.n_scaled; ++j) {
-        const uint32_t t = gen.scaled[j];
-        if (t >= prog->n_tables) return fail(SS_ERR_INVALID, "scaled table %u of %u", t, prog->n_tables);
+    if (gen.n_alpha > (uint32_t)QG_MAX_ALPHA) return fail(SS_ERR_UNSUPPORTED, "%u alpha copies > %d", gen.n_alpha, QG_MAX_ALPHA);
+    Fp two24 = fp_zero(); two24.v[0] = 1u << 24;
+    const Fp two24m = fp_to_mont(two24);
+    uint32_t *adesc = tdesc + 2 * n_desc;
+    for (uint32_t j = 0; j < n_copies; ++j) {
+        const bool is_alpha = j >= gen.n_scaled;
+        const uint32_t t = is_alpha ? gen.alpha[j - gen.n_scaled].table : gen.scaled[j];
+        if (t >= prog->n_tables) return fail(SS_ERR_INVALID, "copied table %u of %u", t, prog->n_tables);
+        if (prog->table_desc[2 * t + 1] > (is_alpha ? QG_MAX_LOG_COPY : 31u)) return fail(SS_ERR_INVALID, "copied table %u has 2^%u entries", t, prog->table_desc[2 * t + 1]);
         const uint64_t len = 1ull << prog->table_desc[2 * t + 1];
-        sc.src[j] = prog->table_desc[2 * t]; sc.dst[j] = (uint32_t)scaled_felts; sc.len[j] = (uint32_t)len;
-        tdesc[2 * (prog->n_tables + j)] = (uint32_t)scaled_felts;
-        tdesc[2 * (prog->n_tables + j) + 1] = (uint32_t)(len - 1ull);
+        if (scaled_felts + len > 0xffffffffull) return fail(SS_ERR_UNSUPPORTED, "the table copies exceed 2^32 entries");
+        Fp factor = two24m;
+        if (is_alpha) {
+            const QGenAlpha &ac = gen.alpha[j - gen.n_scaled];
+            if (ac.constant >= prog->n_consts || ac.form > (uint32_t)QG_ALPHA_R280_UPN) return fail(SS_ERR_INVALID, "alpha copy %u: constant %u, form %u", j - gen.n_scaled, ac.constant, ac.form);
+            factor = qg_alpha_factor(fp_from_limbs64(prog->consts + 4 * (size_t)ac.constant), ac.form);
+            adesc[2 * (j - gen.n_scaled)] = (uint32_t)scaled_felts;
+            adesc[2 * (j - gen.n_scaled) + 1] = (uint32_t)(len - 1ull);
+        } else {
+            tdesc[2 * (prog->n_tables + j)] = (uint32_t)scaled_felts;
+            tdesc[2 * (prog->n_tables + j) + 1] = (uint32_t)(len - 1ull);
+        }
+        uint32_t *c = &host[copies_at + 16 * (size_t)j];
+        c[0] = prog->table_desc[2 * t]; c[1] = (uint32_t)scaled_felts; c[2] = (uint32_t)len;
+        for (int k = 0; k < 8; ++k) c[8 + k] = factor.v[k];
         scaled_felts += len;
     }
-    sc.n = gen.n_scaled;
     const Fp w_dom = root_of_unity(log_N);
     std::vector<uint64_t> part_blocks(gen.n_parts);
     for (uint32_t p = 0; p < gen.n_parts; ++p) {
@@ -2533,12 +2581,9 @@ ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_ai
     for (int c = 0; c < QG_MAX_COLS; ++c) a.cols[c] = c < (int)ncols ? (const Fp *)d_lde_cols[c] : nullptr;
     a.tables = (const Fp *)prog->d_tables;
     a.tables_scaled = (const Fp *)((char *)ctx->scratch + scaled_at);
-    if (sc.n) {
-        sc.tables = a.tables; sc.out = (Fp *)((char *)ctx->scratch + scaled_at);
-        HIP_TRY(launch_qg_scale_tables(s, sc, scaled_felts));
-    }
     a.consts = (const uint32_t *)ctx->scratch;
     a.tdesc = a.consts + (size_t)nc * QG_CONST_STRIDE;
+    a.adesc = a.tdesc + 2 * n_desc;
     a.out = (Fp *)d_out;
     a.sink = (Fp *)((char *)ctx->scratch + ((host.size() * 4 + 63) / 64) * 64);      // inside ensure_scratch's 256 spare bytes
     a.npoints = npoints; a.row0 = (uint32_t)row0; a.log_blowup = log_blowup;
@@ -2559,6 +2604,10 @@ ss_status eval_quotient_compiled(ss_ctx *ctx, const QGenKernel &gen, const ss_ai
         const QGenPart &part = gen.parts[p];
         a.wstep_ptr = reinterpret_cast<const Fp *>(a.consts + wstep_at + 8 * (size_t)p);
         ss_ctx::Scope prof(ctx, SS_PROF_QUOTIENT);
+        // the table copies in front of the first part, inside its stage clock (one entry of the stage's launch count, as before them)
+        if (p == 0 && n_copies)
+            HIP_TRY(launch_qg_copy_tables(s, a.tables, (Fp *)((char *)ctx->scratch + scaled_at), reinterpret_cast<const QgCopy *>(a.consts + copies_at),
+                                          (uint32_t)n_copies, scaled_felts));
         HIP_TRY(part.launch(s, a, (uint32_t)part_blocks[p]));
     }
     return SS_OK;
@@ -2614,6 +2663,12 @@ static ss_status eval_quotient_impl(ss_ctx *ctx, const ss_air_program *prog, con
         for (uint32_t j = 0; baked_ok && j < gen->n_baked; ++j) {
             const QGenBaked &b = gen->baked[j];
             baked_ok = b.index < prog->n_consts && memcmp(prog->consts + 4 * (size_t)b.index, b.value, sizeof(b.value)) == 0;
+        }
+        // ... and read some periodic tables from per-constraint copies (QGenKernel::alpha): a program whose tables there are not short
+        // periodic ones (a trace-length table would be copied once per constraint) is not theirs either
+        for (uint32_t j = 0; baked_ok && j < gen->n_alpha; ++j) {
+            const QGenAlpha &ac = gen->alpha[j];
+            baked_ok = ac.table < prog->n_tables && ac.constant < prog->n_consts && prog->table_desc && prog->table_desc[2 * ac.table + 1] <= QG_MAX_LOG_COPY;
         }
         if (gen && baked_ok && gen->n_consts == prog->n_consts && gen->n_tables == prog->n_tables && gen->ncols <= ncols)
             return eval_quotient_compiled(ctx, *gen, prog, d_lde_cols, ncols, log_N, log_blowup, offset, d_out, row0, N, block ? block_rows : 0);

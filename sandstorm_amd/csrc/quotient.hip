@@ -310,23 +310,22 @@ hipError_t launch_quotient_vm_check(hipStream_t st, const uint32_t *d_code, uint
     return hipGetLastError();
 }
 
-// ---- the compiled kernels' copy of the multiplier-only tables times 2^24 (quotient_gen.h QgScaleArgs; one launch per evaluation:
-// a few thousand to a few hundred thousand entries) - "group sum x zerofier inverse" is then a product with the ten-step reduction
-__global__ __launch_bounds__(256) void qg_scale_tables_kernel(QgScaleArgs a, uint64_t total) {
-    Fp two24 = fp_zero(); two24.v[0] = 1u << 24;
-    const Fp f = fp_to_mont(two24);
+// ---- the compiled kernels' copies of the multiplier-only tables (quotient_gen.h QgCopy; one launch per evaluation).  Times 2^24:
+// "group sum x zerofier inverse" is then a product with the ten-step reduction.  Times a constraint's coefficient in one of the
+// constant forms (the alpha copies): "constraint x coefficient x zerofier inverse" is then one term of the part's wide sum.  A few
+// hundred thousand to a few million entries, whatever the trace length; every entry comes out canonical (fp_mul).
+__global__ __launch_bounds__(256) void qg_copy_tables_kernel(const Fp *tables, Fp *out, const QgCopy *copies, uint32_t n, uint64_t total) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t j = 0;
-        while (j + 1 < a.n && i >= a.dst[j + 1]) ++j;          // the copies lie one after the other: table j covers [dst[j], dst[j] + len[j])
-        a.out[i] = fp_mul(a.tables[a.src[j] + (i - a.dst[j])], f);
+        Fp r;
+        if (qg_copy_entry(copies, n, i, [tables](uint32_t index) { return qg_load_raw(tables, index); }, &r)) qg_store(out + i, r);
     }
 }
 
-hipError_t launch_qg_scale_tables(hipStream_t st, const QgScaleArgs &a, uint64_t total_felts) {
-    if (a.n == 0 || total_felts == 0) return hipSuccess;
-    uint32_t blocks = (uint32_t)((total_felts + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(qg_scale_tables_kernel, dim3(blocks), dim3(256), 0, st, a, total_felts);
+hipError_t launch_qg_copy_tables(hipStream_t st, const Fp *tables, Fp *out, const QgCopy *d_copies, uint32_t n_copies, uint64_t total_felts) {
+    if (n_copies == 0 || total_felts == 0) return hipSuccess;
+    uint64_t blocks = (total_felts + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(qg_copy_tables_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, tables, out, d_copies, n_copies, total_felts);
     return hipGetLastError();
 }
 

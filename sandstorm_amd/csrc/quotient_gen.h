@@ -36,6 +36,7 @@ struct QGenArgs {
     uint32_t trace_mask;                         // trace cells are read at (k + shift) & trace_mask: N - 1 on whole columns, ~0 on a
     uint32_t log_blowup;                         // row block that carries the rows behind it (ss_eval_quotient_rows)
     const Fp *derived[QG_MAX_DERIVED];           // the derived columns (quotient_derive.h; made per launch), indexed like the trace columns
+    const uint32_t *adesc;                       // per alpha copy (QGenKernel::alpha): first element in tables_scaled, index mask
 };
 
 // One compiled program = one or more kernels ("parts", tools/gen_quotient.py split_program) whose outputs sum to the
@@ -61,20 +62,21 @@ struct QGenKernel {
     QGenPart parts[QG_MAX_PARTS];
     uint32_t n_baked;                            // constants held as code: a program whose table differs in one of them is interpreted
     const QGenBaked *baked;
+    uint32_t n_alpha;                            // alpha copies the kernels read through QG_TABLE_ALPHA_RAW (quotient_derive.h): copy j is
+    const QGenAlpha *alpha;                      // entry j
     uint32_t n_scaled;                           // tables the kernels read from a 2^24-fold copy (multiplier-only tables): their numbers;
     const uint32_t *scaled;                      // copy j is addressed by descriptor n_tables + j
     uint32_t n_derived;                          // derived columns the kernels read through QG_DERIVED_RAW (quotient_derive.h)
     QGenDerived derived[QG_MAX_DERIVED];
 };
 
-// the launch's copy of the multiplier-only tables times 2^24 (csrc/quotient.hip qg_scale_tables_kernel)
+// the launch's copies of the multiplier-only tables (csrc/quotient.hip qg_copy_tables_kernel, quotient_derive.h QgCopy): the scaled
+// tables (factor 2^24) and the alpha copies (factor: a constant's form) are made by ONE launch; the descriptors come through device
+// memory - a few hundred of them do not fit the kernel-argument block
 static constexpr int QG_MAX_SCALED = 48;
-struct QgScaleArgs {
-    const Fp *tables;
-    Fp *out;
-    uint32_t n, src[QG_MAX_SCALED], dst[QG_MAX_SCALED], len[QG_MAX_SCALED];      // per table: first element in `tables`, in `out`, elements
-};
-hipError_t launch_qg_scale_tables(hipStream_t st, const QgScaleArgs &a, uint64_t total_felts);
+static constexpr int QG_MAX_ALPHA = 1024;
+static constexpr uint32_t QG_MAX_LOG_COPY = 20;  // an alpha-copied table has at most 2^20 entries: a period (<= 2^15) times the blow-up (<= 16), doubled
+hipError_t launch_qg_copy_tables(hipStream_t st, const Fp *tables, Fp *out, const QgCopy *d_copies, uint32_t n_copies, uint64_t total_felts);
 // rows 0 .. rows - 1 of a derived column of `col` (csrc/quotient.hip qg_derive_column_kernel): the caller guarantees that
 // (k + (off << log_blowup)) & trace_mask lies inside `col` for every k < rows and every term's offset
 hipError_t launch_qg_derive_column(hipStream_t st, const QGenDerived &d, const Fp *col, Fp *out, uint64_t rows, uint32_t log_blowup, uint32_t trace_mask);
@@ -140,12 +142,27 @@ __device__ __forceinline__ void qg_wide_tail(QgWide &w, const Fl &l) {
     for (int j = 0; j < 9; ++j) w.c[9 + j] += (u64)l.l[j] << 4;
 }
 
+// QG_PIN_WIDE(w), behind a term whose factor is an alpha copy: the copy's entry sits in a prefetch register, so - unlike a constant,
+// whose LDS read no barrier lets pass - nothing ties the term's 81 multiply-adds to their place, and the compiler sinks the terms of
+// a whole group to the sum's reduction, every constraint's value spilled until then (starknet part 0: 152 -> 1124 bytes of scratch per
+// lane).  An empty statement that names the 19 columns as read and written keeps them where the generator put them.
+__device__ __forceinline__ void qg_pin_wide(QgWide &w) {
+#ifdef __AMDGCN__                                // (vector-register operands: the device compilation only)
+    asm volatile("" : "+v"(w.c[0]), "+v"(w.c[1]), "+v"(w.c[2]), "+v"(w.c[3]), "+v"(w.c[4]), "+v"(w.c[5]), "+v"(w.c[6]), "+v"(w.c[7]), "+v"(w.c[8]), "+v"(w.c[9]));
+    asm volatile("" : "+v"(w.c[10]), "+v"(w.c[11]), "+v"(w.c[12]), "+v"(w.c[13]), "+v"(w.c[14]), "+v"(w.c[15]), "+v"(w.c[16]), "+v"(w.c[17]), "+v"(w.c[18]));
+#else
+    (void)w;
+#endif
+}
+#define QG_PIN_WIDE(w) qg_pin_wide(w);
+
 // operands (the generator writes these with immediates).  `idx` is the point's local index: this point's, or the next
 // point's for the loads issued across the loop edge.
 #define QG_TRACE_RAW(col, off, idx) qg_load_raw(a.cols[col], ((idx) + ((off) << lb)) & maskN)
 #define QG_DERIVED_RAW(d, off, idx) qg_load_raw(a.derived[d], ((idx) + ((off) << lb)) & maskN)
 #define QG_TABLE_RAW(t, idx) qg_load_raw(a.tables + tdesc[2 * (t)], ((idx) + row0) & tdesc[2 * (t) + 1])
 #define QG_TABLE_SCALED_RAW(t, idx) qg_load_raw(a.tables_scaled + tdesc[2 * (t)], ((idx) + row0) & tdesc[2 * (t) + 1])
+#define QG_TABLE_ALPHA_RAW(j, idx) qg_load_raw(a.tables_scaled + adesc[2 * (j)], ((idx) + row0) & adesc[2 * (j) + 1])
 #define QG_CONST(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k))
 #define QG_CONST_R280(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k) + 9)
 #define QG_CONST_R280_UP(k) qg_const_lds(lds_consts + QG_CONST_LDS_STRIDE * (k) + 18)
@@ -208,6 +225,7 @@ static inline size_t qg_lds_bytes(int nconsts, int nslots) {
     const uint64_t lane = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;                            \
     const uint32_t lb = a.log_blowup, maskN = a.trace_mask, row0 = a.row0;                            \
     const uint32_t *tdesc = a.tdesc;                                                                  \
+    const uint32_t *adesc = a.adesc; (void)adesc;                                                     \
     Fl x = fl_from_fp(fp_mul(a.offset, fp_pow_u64(a.w, lane)));                                       \
     QG_DECLARE_SLOTS
 

@@ -313,6 +313,8 @@ def compact_slots(ins):
 TEMP_ACC = 4            # a fifth accumulator the generator may use (the program format has four)
 SRC_DERIVED = 6         # an operand kind of the generator's own (the program format has six): a cell of a DERIVED COLUMN,
                         # w1 = (derived column << 24) | row offset - see derived_column_of
+SRC_TALPHA = 7          # another one: a cell of an ALPHA COPY of a multiplier-only periodic table - the table times one constraint's
+                        # coefficient (fold_alpha_tables); w1 = (table << 16) | constant
 MAX_DERIVED = 2         # derived columns per layout (each costs the launch one column of scratch and one streaming pass)
 # ... and the loads a column has to save per point to be given that pass and that memory.  Measured (2^25 points,
 # profiles/quotient_derived_flag_column.json): the flag column saves 100 loads per point and 4.0 ms of starknet's first part for a
@@ -416,6 +418,125 @@ def encode(ins):
     return code
 
 
+def fold_alpha_tables(ins, scaled_tables, report=None):
+    """A zerofier group is  (sum_k alpha^k C_k) x T  added to the part's total: a ten-step reduction of the group's sum and a full
+    product by the domain's multiplier table T at every point.  Where T is a multiplier-only periodic table (`scaled_tables`: at most
+    2^17 entries whatever the trace length) the launch can make one copy of it per constraint, T'_k = alpha^k T (times 2^24 and a sign,
+    as the constant forms do), and since (sum_k alpha^k C_k) T = sum_k C_k (alpha^k T) every constraint is then one term of the part's
+    total: the group's reduction and product are gone.  This pass rewrites the instruction stream accordingly:
+
+        [C_0 in g]; MUL g, alpha^k0;  [C_1 in e]; MUL e, alpha^k1; ADD g, e;  ...;  MUL g, TABLE t;  ADD tot, g     becomes
+        [C_0 in g]; MUL g, T'(t, k0); ADD tot, g;  [C_1 in e]; MUL e, T'(t, k1); ADD tot, e;  ...
+
+    with operands of the generator's own kind SRC_TALPHA ("MOV tot, g" at the tail - the part's first group - makes the first
+    constraint's addition the move).  Taken only where the stream has exactly that shape: the group's sum is used by the table
+    product alone, every term of it is a product by a constant used once, the additions go into g, and nothing between the group's
+    first coefficient and its tail touches `tot`.  Groups with a further factor (X - g^e) behind the table, and the full-length
+    inverse tables of the single-row domains, do not match and stay as they are.
+    -> (program, groups folded, constraints folded, the new program's pcs of each folded group's last addition into the total)"""
+    nodes, made_at, lhs = [], {}, {}
+
+    def new(kind, a=None, b=None):
+        nodes.append((kind, a, b))
+        return len(nodes) - 1
+    acc, slot = [None] * 8, {}
+    for pc, (op, d, kind, w1) in enumerate(ins):
+        src = None
+        if op <= OP_MUL:
+            src = acc[w1 & 7] if kind == SRC_ACC else slot.get(w1) if kind == SRC_SLOT else new("LEAF")
+        if op == OP_MOV:
+            acc[d] = src
+        elif op in (OP_ADD, OP_SUB, OP_MUL):
+            lhs[pc] = acc[d]
+            acc[d] = new({OP_ADD: "ADD", OP_SUB: "SUB", OP_MUL: "MUL"}[op], acc[d], src)
+            made_at[acc[d]] = pc
+        elif op == OP_RSUB:
+            acc[d] = new("SUB", src, acc[d])
+            made_at[acc[d]] = pc
+        elif op == OP_INV:
+            acc[d] = new("INV", acc[d])
+        elif op == OP_ST:
+            slot[w1] = acc[d]
+        elif op == OP_OUT:
+            new("OUT", acc[d])
+    uses = {}
+    for kind, a, b in nodes:
+        for x in (a, b):
+            if x is not None:
+                uses[x] = uses.get(x, 0) + 1
+    node_at = {k: v for v, k in made_at.items()}
+    drop, replace, after, group_last = set(), {}, {}, []
+    groups = constraints = seen_groups = 0
+    for pc in range(len(ins) - 1):
+        op, g, kind, t = ins[pc]
+        op2, tot, kind2, w2 = ins[pc + 1]
+        if not (op == OP_MUL and kind == SRC_TABLE and t in scaled_tables):
+            continue
+        why = None
+        if not (op2 in (OP_ADD, OP_MOV) and kind2 == SRC_ACC and (w2 & 7) == g and tot != g):
+            why = "the product is not added to a total"
+        elif uses.get(node_at[pc], 0) != 1:
+            why = "the product is used again"
+        terms, inner, stack = [], [], [lhs[pc]]
+        while why is None and stack:
+            v = stack.pop()
+            if v is None:
+                why = "an empty operand"
+            elif nodes[v][0] == "ADD" and uses.get(v, 0) == 1:
+                inner.append(v)
+                stack += [nodes[v][1], nodes[v][2]]
+            else:
+                terms.append(v)
+        if why is None:
+            for v in terms:
+                k = made_at.get(v)
+                if nodes[v][0] != "MUL" or uses.get(v, 0) != 1 or k is None or ins[k][0] != OP_MUL or ins[k][2] != SRC_CONST or k in replace:
+                    why = "a term that is not a product by a constant used once"
+                    break
+        if why is None:
+            term_pcs = sorted(made_at[v] for v in terms)
+            adds = sorted(made_at[v] for v in inner)
+            # the first constraint is computed in g itself, every other one in an accumulator that is then added to g
+            if ins[term_pcs[0]][1] != g or len(adds) != len(term_pcs) - 1:
+                why = "the sum does not start in the group's accumulator"
+            for k, a_pc in zip(term_pcs[1:], adds):
+                e = ins[k][1]
+                if ins[a_pc] != (OP_ADD, g, SRC_ACC, e) or e in (g, tot) or not k < a_pc:
+                    why = "an addition of another shape"
+            for q in range(term_pcs[0], pc):
+                qop, qd, qkind, qw1 = ins[q]
+                if qd == tot or (qop <= OP_MUL and qkind == SRC_ACC and (qw1 & 7) == tot):
+                    why = "the total's accumulator is used inside the group"
+                    break
+        if why is None and "QG_ALPHA_SKIP" in os.environ and str(seen_groups) in os.environ["QG_ALPHA_SKIP"].split(","):
+            why = "skipped by QG_ALPHA_SKIP"
+        seen_groups += 1 if (why is None or why.startswith("skipped")) else 0
+        if why is not None:
+            if report is not None:
+                report.append("table %d at pc %d stays a product: %s" % (t, pc, why))
+            continue
+        for n_, k in enumerate(term_pcs):
+            e, c = ins[k][1], ins[k][3]
+            assert t < (1 << 15) and c < (1 << 16)
+            replace[k] = (OP_MUL, e, SRC_TALPHA, (t << 16) | c)
+            after[k] = (OP_MOV if op2 == OP_MOV and n_ == 0 else OP_ADD, tot, SRC_ACC, e)
+        drop.update(adds)
+        drop.update((pc, pc + 1))
+        group_last.append(term_pcs[-1])
+        groups += 1
+        constraints += len(term_pcs)
+    out, ends, last_of_group = [], set(), set(group_last)
+    for pc, instr in enumerate(ins):
+        if pc in drop:
+            continue
+        out.append(replace.get(pc, instr))
+        if pc in after:
+            out.append(after[pc])
+            if pc in last_of_group:
+                ends.add(len(out) - 1)
+    return out, groups, constraints, ends
+
+
 PREFETCH_DEPTH = 6      # memory operands in flight ahead of their use (one wave per SIMD: nothing else hides the latency)
 LAZY_PRODUCT_MAX = int(os.environ.get("QG_LAZY_PRODUCT", "0"))   # bound(a) x bound(b) a plain product takes without reducing a factor first
 DOT_MAX_TERMS = 16      # products accumulated in the 64-bit columns before a Montgomery reduction (16 * 9 * 2^56 < 2^64)
@@ -489,6 +610,7 @@ def generate(layout, all_variants=False):
             full_length = {t for t, spec in enumerate(template_program.specs[layout]) if spec[0] == "inverse"}
             scaled = sorted(t for t, ops in uses.items() if ops == {OP_MUL} and t not in full_length)
         names, baked = [], set()
+        alpha = []                                  # the layout's alpha copies, in the order the bodies number them: (table, constant, form)
         # the parts that rematerialise (the decoded flags: recomputed at their uses instead of parked, 17 -> 6 slots) - and what of
         # that is a row of a derived column, read instead of recomputed (one list per layout: the launch builds the columns once)
         compacted = [compact_slots(part) for part in parts]
@@ -509,8 +631,20 @@ def generate(layout, all_variants=False):
                 lds = part_slots * 2 * threads * 16 + n_consts * 36 * 4
                 assert lds * wgs <= LDS_BYTES_PER_CU, "%s%s part %d: %d slots + constants = %d B of LDS x %d workgroups per CU" % (layout, suffix, j, part_slots, lds, wgs)
             base = "quotient_gen_%s%s_p%d" % (layout, suffix, j)
-            wide_here, depth_here, lazy_sub, const_factor, min_terms, small_here, dedup_here = PART_TUNING.get(layout, {}).get((suffix, j), (False, depth, False, False, 1, False, False))
-            small_here = os.environ["QG_SMALL_MULTIPLES"] != "0" if "QG_SMALL_MULTIPLES" in os.environ else small_here      # A/B builds: every part alike
+            wide_here, depth_here, lazy_sub, const_factor, min_terms, small_here, dedup_here, alpha_here = (
+                PART_TUNING.get(layout, {}).get((suffix, j), (False, depth, False, False, 1, False, False, False)) + (False,))[:8]
+            if "QG_ALPHA_TABLES" in os.environ:               # A/B builds: "all", "0", or "starknet:1,starknet:3,..."
+                alpha_here = os.environ["QG_ALPHA_TABLES"] == "all" or ("%s:%d" % (layout, j)) in os.environ["QG_ALPHA_TABLES"].split(",")
+            alpha_flush = os.environ.get("QG_ALPHA_FLUSH", alpha_here if isinstance(alpha_here, str) else "never")
+            alpha_here = bool(alpha_here) and fuse and bool(scaled)
+            group_ends = set()
+            if alpha_here:
+                report = []
+                part, n_groups, n_folded, group_ends = fold_alpha_tables(part, set(scaled), report)
+                print("%s part %d: %d groups (%d constraints) take their coefficients from alpha copies of their tables" % (layout, j, n_groups, n_folded))
+                if os.environ.get("QG_VERBOSE"):
+                    print("".join("   %s\n" % line for line in report), end="")
+            small_here =os.environ["QG_SMALL_MULTIPLES"] != "0" if "QG_SMALL_MULTIPLES" in os.environ else small_here      # A/B builds: every part alike
             dedup_here = os.environ["QG_DEDUP"] != "0" if "QG_DEDUP" in os.environ else dedup_here
             min_terms = int(os.environ.get("QG_WIDE_MIN_TERMS", min_terms))
             if "QG_WIDE_PARTS" in os.environ:                 # A/B builds (tools/qg_wide_ab.sh): the same choice for every part
@@ -520,16 +654,39 @@ def generate(layout, all_variants=False):
             const_factor = os.environ["QG_CONST_FACTOR"] != "0" if "QG_CONST_FACTOR" in os.environ else const_factor
             body = generate_body(layout, part, n_consts, part_slots, n_tables, ncols, depth_here, base + ".inc", fuse,
                                  "QG_OUT" if j == 0 else "QG_OUT_ACC", sync, wide_here, lazy_sub, const_factor, min_terms, scaled, derived=derived,
-                                 small=template_program.structural[layout] if small_here else {}, dedup=dedup_here)
+                                 small=template_program.structural[layout] if small_here else {}, dedup=dedup_here,
+                                 alpha=alpha if alpha_here else None, group_ends=group_ends if alpha_flush == "group" else ())
             baked.update(body["baked"])
             write_part(layout, suffix, j, len(parts), base, body, len(part), n_consts, part_slots, slots_in_regs, wgs, fence, threads, sync)
             names.append(base + ".hip")
         write_kernel_table(layout, suffix, k, code, n_consts, n_tables, ncols, len(parts), scaled, derived,
-                           [(c, template_program.structural[layout][c][1]) for c in sorted(baked)])
+                           [(c, template_program.structural[layout][c][1]) for c in sorted(baked)], alpha)
+        if k == 0:
+            report_alpha_scratch(layout, alpha)
         names.append("quotient_gen_%s%s.hip" % (layout, suffix))
         written.append((k, suffix, names))
     return written
 
+
+
+ALPHA_PIN = os.environ.get("QG_ALPHA_PIN", "1") != "0"         # QG_PIN_WIDE behind the terms by alpha copies (A/B: QG_ALPHA_PIN=0)
+ALPHA_FORMS = ("R280", "R280_UP", "R280_UPN")       # an alpha copy is its table times the constant in one of the constant forms of quotient_gen.h
+
+
+def report_alpha_scratch(layout, alpha):
+    """what the alpha copies add to the launch's scratch: 32 bytes per entry of every copy - the periods times the blow-up, whatever the
+    trace length (printed at blow-up 2; it doubles with the blow-up as the scaled tables do)"""
+    import importlib
+    lay = importlib.import_module("sandstorm_amd.layouts." + layout)
+    tables = lay.Tables(1 << (21 if layout == "starknet" else 18))         # the template's size: its specs name powers of X by n / period
+    specs = template_program.specs[layout]
+    entries = 0
+    for t, _, _ in alpha:
+        assert specs[t][0] != "inverse"
+        entries += tables.length(specs[t])
+    print("%s: %d alpha copies of %d tables, %d entries = %d bytes of scratch per launch at blow-up 2"
+          % (layout, len(alpha), len(set(t for t, _, _ in alpha)), entries, 32 * entries))
+    return entries
 
 
 WIDE_MAX_OTHER_PRODUCTS = int(os.environ.get("QG_WIDE_OTHER", "0"))     # other multiplications allowed while a constraint's wide sum is open
@@ -554,10 +711,10 @@ WIDE_MAX_SPAN = int(os.environ.get("QG_WIDE_SPAN", "1000"))            # program
 # A part whose scratch (spill) bytes grow under a cut keeps that cut off - the condition the cuts were taken under, checked on the
 # cross-compiled kernels: part 1 spills 76 -> 104 bytes per lane with its two small multiples (off), part 3 0 -> 272 with its 21
 # repeated operands as single loads (off: the shared register lives across the fence between its two uses).
-PART_TUNING = {"starknet": {("", 0): (True, 3, True, True, 1, True, True), ("", 1): (True, 2, True, True, 1, False, True),
-                            ("", 2): (True, 3, False, False, 1, True, True), ("", 3): (True, 3, True, True, 2, True, False),
-                            ("", 4): (True, 2, False, False, 2, True, True), ("", 5): (True, 3, True, True, 1, True, True)},
-               "recursive": {("", 0): (True, 2, True, True, 1, True, True),
+PART_TUNING = {"starknet": {("", 0): (True, 3, True, True, 1, True, True, True), ("", 1): (True, 2, True, True, 1, False, True, True),
+                            ("", 2): (True, 3, False, False, 1, True, True, True), ("", 3): (True, 3, True, True, 2, True, False, True),
+                            ("", 4): (True, 2, False, False, 2, True, True, True), ("", 5): (True, 3, True, True, 1, True, True, True)},
+               "recursive": {("", 0): (True, 2, True, True, 1, True, True, "group"),
                              ("_v2", 0): (True, 2, True, True, 1, False, False), ("_v2", 1): (True, 2, True, True, 1, False, False),
                              ("_v3", 0): (True, 2, True, True, 1, False, False), ("_v3", 1): (True, 2, True, True, 1, False, False),
                              ("_v3", 2): (True, 2, True, True, 1, False, False)}}
@@ -611,7 +768,7 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
             acc[d] = new("SUB", src, acc[d])
             made_at[acc[d]] = pc
         elif op == OP_MUL:
-            if pc in fused or (WIDE_ANY_CONST_MUL and kind == SRC_CONST):      # any scaling by a constant can take the 2^24 back
+            if pc in fused or (WIDE_ANY_CONST_MUL and kind in (SRC_CONST, SRC_TALPHA)):      # any scaling by a constant can take the 2^24 back (an alpha copy too)
                 root_of[pc] = acc[d]
             if src in small_node or acc[d] in small_node:
                 small_mul.add(pc)
@@ -676,12 +833,14 @@ def plan_wide_constraints(ins, fused, banned, const_factor=True, min_terms=1, sc
 
 
 def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPTH, inc_name, FUSE_ALPHA_DOT_PRODUCTS=False, out_macro="QG_OUT",
-                  sync_every=0, wide_products=False, lazy_sub=False, const_factor=False, min_terms=1, scaled_tables=(), derived=(), small=None, dedup=False):
+                  sync_every=0, wide_products=False, lazy_sub=False, const_factor=False, min_terms=1, scaled_tables=(), derived=(), small=None, dedup=False, alpha=None, group_ends=()):
     """the straight-line body of one (part) program -> csrc/<inc_name>.  `derived`: the derived columns SRC_DERIVED operands name
     (rematerialize_cheap_slots); the body reads them through QG_DERIVED_RAW and carries a fallback definition of that macro over
     the real column, for a harness that defines only the other operand macros and fills only the real columns.
     `small`: the structural small constants whose multiples may be written as shifts and adds (structural_constants; {} = none).
-    `dedup`: two consecutive memory operands that name the same cell are one load."""
+    `dedup`: two consecutive memory operands that name the same cell are one load.
+    `alpha`: the layout's list of alpha copies (table, constant, form) if the program holds SRC_TALPHA operands (fold_alpha_tables): the
+    body's copies are appended to it, and QG_TABLE_ALPHA_RAW(j, idx) reads copy j of that list."""
     small = small or {}
     n_instr = len(ins)
     # ---- memory operands in program order: loaded PREFETCH_DEPTH operands ahead into a rotating set of registers
@@ -700,6 +859,9 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
                 mem_ops.append((pc, "QG_TABLE_SCALED_RAW(%d, %%s)" % (n_tables + list(scaled_tables).index(w1))))
             else:
                 mem_ops.append((pc, "QG_TABLE_RAW(%d, %%s)" % w1))
+        elif op == OP_MUL and kind == SRC_TALPHA:
+            assert alpha is not None and (w1 >> 16) in scaled_tables and (w1 & 0xffff) < n_consts
+            mem_ops.append((pc, ("alpha copy", w1 >> 16, w1 & 0xffff)))          # which form: known with the plan (below)
     # "x + x" on a cell is MOV acc, T; ADD acc, T: the second operand is the first one's register, which is freed (its next load
     # issued) after the second use.  Only CONSECUTIVE operands: a register kept across other loads is a live range the allocator pays
     # for (profiles/r06_call_q_quotient_conversions_ablated.txt)
@@ -726,14 +888,28 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
     for pc in range(n_instr - 1):
         op, e, kind, w1 = ins[pc]
         op2, d2, kind2, w2 = ins[pc + 1]
-        if FUSE_ALPHA_DOT_PRODUCTS and op == OP_MUL and kind == SRC_CONST and op2 == OP_ADD and kind2 == SRC_ACC and (w2 & 7) == e and d2 != e and dies_after(e, pc + 1):
+        if FUSE_ALPHA_DOT_PRODUCTS and op == OP_MUL and kind in (SRC_CONST, SRC_TALPHA) and op2 == OP_ADD and kind2 == SRC_ACC and (w2 & 7) == e and d2 != e and dies_after(e, pc + 1):
             fused[pc] = d2
     banned = set()
     while True:                                     # constraints whose half-summed value is used in a way the emission cannot express
         try:                                        # go back to plain products, one at a time (plan_wide_constraints)
-            out, stats = _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, sync_every, lazy_sub, const_factor, set(scaled_tables),
-                                    plan_wide_constraints(ins, fused, banned, const_factor, min_terms, set(scaled_tables), set(small)) if wide_products and FUSE_ALPHA_DOT_PRODUCTS else ({}, {}, {}),
-                                    small)
+            plan = plan_wide_constraints(ins, fused, banned, const_factor, min_terms, set(scaled_tables), set(small)) if wide_products and FUSE_ALPHA_DOT_PRODUCTS else ({}, {}, {})
+            # an alpha copy carries what the constant would: the plain R280 form, or - where the multiplication takes a constraint's own
+            # wide sum back - the form with 2^24 more and the sum's sign.  Copies are numbered across the layout's parts, in order of use
+            copies = list(alpha or ())
+            ops = []
+            for pc_, text in mem_ops:
+                if isinstance(text, tuple):
+                    key = (text[1], text[2], 0 if pc_ not in plan[1] else 1 if plan[1][pc_][0] > 0 else 2)
+                    if key not in copies:
+                        copies.append(key)
+                    text = "QG_TABLE_ALPHA_RAW(%d, %%s)" % copies.index(key)
+                ops.append((pc_, text))
+            out, stats = _emit_body(ins, n_consts, n_slots, ops, mem_index, D, fused, out_macro, sync_every, lazy_sub, const_factor, set(scaled_tables),
+                                    plan, small, flush_on_switch=alpha is not None, flush_after=set(group_ends))
+            mem_ops = ops
+            if alpha is not None:
+                alpha[:] = copies
             break
         except WideViolation as e:
             banned.add(e.k)
@@ -744,9 +920,14 @@ def generate_body(layout, ins, n_consts, n_slots, n_tables, ncols, PREFETCH_DEPT
     regs = "    Fp " + ", ".join("m%d" % k for k in range(D)) + ";\n"
     prime = "".join("    m%d = %s;\n" % (j, mem_ops[j][1] % "i32") for j in range(D))
     used = sorted(set(w1 >> 24 for op, _, kind, w1 in ins if op <= OP_MUL and kind == SRC_DERIVED))
-    inc = _INC_TEMPLATE % dict(layout=layout, regs=regs, prime=prime, body=body, depth=D, derived_begin=_derived_fallback(derived, used),
+    import re
+    used_alpha = sorted(set(int(j_) for _, text in mem_ops for j_ in re.findall(r"QG_TABLE_ALPHA_RAW\((\d+),", text)))
+    stats["alpha_copies"] = len(used_alpha)
+    inc = _INC_TEMPLATE % dict(layout=layout, regs=regs, prime=prime, body=body, depth=D,
+                               derived_begin=_alpha_fallback(alpha, used_alpha, n_tables, list(scaled_tables)) + _derived_fallback(derived, used),
                                small_begin=_SMALL_FALLBACK_BEGIN if stats["baked"] else "", small_end=_SMALL_FALLBACK_END if stats["baked"] else "",
-                               derived_end=_DERIVED_FALLBACK_END % "".join("#undef QG_DERIVED_FALLBACK_%d\n" % k for k in used) if used else "",
+                               derived_end=(_DERIVED_FALLBACK_END % "".join("#undef QG_DERIVED_FALLBACK_%d\n" % k for k in used) if used else "")
+                                           + (_ALPHA_FALLBACK_END % "".join("#undef QG_TABLE_ALPHA_FALLBACK_%d\n" % k for k in used_alpha) if used_alpha else ""),
                                wide=("    QgWide wd;\n" if stats["fused"] else "") + ("    QgWide wq;\n" if stats["wide_terms"] else ""),
                                temp_acc=", acc4 = fl_zero()" if any(d == TEMP_ACC for _, d, _, _ in ins) else "")
     name = inc_name
@@ -829,6 +1010,31 @@ def _derived_fallback(derived, used):
     return "\n".join(lines) + "\n"
 
 
+def _alpha_fallback(alpha, used, n_tables, scaled_tables):
+    """QG_TABLE_ALPHA_RAW where nobody defined it: an entry of alpha copy j computed from the table's scaled copy and the constant table"""
+    if not used:
+        return ""
+    lines = ["// Operands QG_TABLE_ALPHA_RAW(j, idx) are entries of ALPHA COPIES of multiplier-only periodic tables (tools/gen_quotient.py",
+             "// fold_alpha_tables): copy j is a table times one constraint's coefficient in one of the constant forms - the launch makes them",
+             "// behind the scaled tables (csrc/quotient.hip qg_copy_tables_kernel).  Where the includer does not define the macro, the entry is",
+             "// the product of the scaled table's entry by that form of the constant - the same value mod p, fully reduced.",
+             "#ifndef QG_TABLE_ALPHA_RAW", "#define QG_TABLE_ALPHA_FALLBACK", "#define QG_TABLE_ALPHA_RAW(j, idx) QG_TABLE_ALPHA_FALLBACK_##j(idx)",
+             "#define QG_PIN_WIDE(w)", "#endif",
+             "#ifdef QG_TABLE_ALPHA_FALLBACK"]
+    for j in used:
+        t, c, form = alpha[j]
+        lines.append("#define QG_TABLE_ALPHA_FALLBACK_%d(idx) fl_to_fp(fl_mul_r280(fl_from_fp(QG_TABLE_SCALED_RAW(%d, idx)), QG_CONST_%s(%d)))"
+                     % (j, n_tables + scaled_tables.index(t), ALPHA_FORMS[form], c))
+    lines.append("#endif")
+    return "\n".join(lines) + "\n"
+
+
+_ALPHA_FALLBACK_END = '''#ifdef QG_TABLE_ALPHA_FALLBACK
+%s#undef QG_TABLE_ALPHA_RAW
+#undef QG_PIN_WIDE
+#undef QG_TABLE_ALPHA_FALLBACK
+#endif
+'''
 _DERIVED_FALLBACK_END = '''#ifdef QG_DERIVED_FALLBACK
 %s#undef QG_DERIVED_RAW
 #undef QG_DERIVED_FALLBACK
@@ -836,7 +1042,7 @@ _DERIVED_FALLBACK_END = '''#ifdef QG_DERIVED_FALLBACK
 '''
 
 
-def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, sync_every, SUB_LAZY2, CONST_FACTOR, SCALED, plan, small=None):
+def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, sync_every, SUB_LAZY2, CONST_FACTOR, SCALED, plan, small=None, flush_on_switch=False, flush_after=()):
     """one pass over the (part) program: -> (lines, stats); raises WideViolation"""
     n_instr = len(ins)
     wide_mul, wide_close, wide_struct = plan
@@ -844,7 +1050,7 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
     emit = out.append
     bound = [1, 1, 1, 1, 1]                        # four accumulators of the program format + the generator's own (TEMP_ACC)
     stats = {"mul": 0, "mulr": 0, "reduce": 0, "loads": len(mem_ops), "fused": 0, "flushes": 0, "wide_terms": 0, "wide_closes": 0, "wide_neg": 0,
-             "baked": {}}                          # baked: constant -> multiplications by it written as shifts and adds
+             "alpha_terms": 0, "baked": {}}                          # baked: constant -> multiplications by it written as shifts and adds
     small = small or {}
     last_use = {}                                  # memory operand -> the last instruction that reads it (repeated operands share one)
     for pc_, q_ in mem_index.items():
@@ -941,6 +1147,8 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
         if sync_every and pc and pc % sync_every == 0:
             emit("    QG_SYNC")
         if pc in skip_add:                          # the ADD of a fused pair: already accounted in the wide accumulator
+            if pc in flush_after:
+                flush_wide()
             continue
         # any other touch of the accumulator that carries a pending dot product needs its value: flush first
         touches = {d} | ({w1 & 7} if op <= OP_MUL and kind == SRC_ACC else set())
@@ -958,7 +1166,7 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
             elif kind == SRC_CONST:
                 assert w1 < n_consts
                 src = ("QG_CONST_R280(%d)" if op == OP_MUL else "QG_CONST(%d)") % w1
-            elif kind in (SRC_TRACE, SRC_TABLE, SRC_DERIVED):
+            elif kind in (SRC_TRACE, SRC_TABLE, SRC_DERIVED, SRC_TALPHA):
                 src = "fl_from_fp(m%d)" % (mem_index[pc] % D)
             else:
                 assert kind == SRC_X
@@ -1026,9 +1234,12 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
                 wq.update(k=None, units=0, terms=0)
                 stats["wide_closes"] += 1
                 closed_here = True
-                src = ("QG_CONST_R280_UP(%d)" if g > 0 else "QG_CONST_R280_UPN(%d)") % w1
+                if kind == SRC_CONST:                              # (an alpha copy was chosen in that form: generate_body)
+                    src = ("QG_CONST_R280_UP(%d)" if g > 0 else "QG_CONST_R280_UPN(%d)") % w1
             elif sm or dm:
                 raise WideViolation((sm or dm)["k"], "multiplied at pc %d" % pc)
+            if kind == SRC_TALPHA and (pc in wide_close) != closed_here:
+                raise WideViolation(pc, "planned to close a wide sum that is not there")
         elif op in (OP_INV, OP_OUT) and wacc[d] is not None:
             raise WideViolation(wacc[d]["k"], "used at pc %d" % pc)
 
@@ -1146,12 +1357,14 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
                         if plan_[0][0] == "R":
                             reduce_acc(d)
                         scaling = (w1, plan_ + (bound[d],), v)
-                elif kind != SRC_CONST and const_before is not None and const_before in small and not (kind == SRC_TABLE and w1 in SCALED):
+                elif kind not in (SRC_CONST, SRC_TALPHA) and const_before is not None and const_before in small and not (kind == SRC_TABLE and w1 in SCALED):
                     plan_ = small_multiple(const_before, sb, PRODUCT_COST)
                     if plan_ is not None and not (plan_[0][0] == "R" and src_acc is None):
                         if plan_[0][0] == "R":
                             reduce_src()
                         scaling = (const_before, plan_ + (sb,), src)
+            if flush_on_switch and scaling is None and tgt is not None and wide["acc"] not in (None, tgt):
+                flush_wide()                                   # the part's total gives way to a group's own sum, and back
             if scaling is not None:
                 emit_scaled(scaling[0], scaling[1], d, scaling[2])
             elif tgt is not None and (wide["acc"] in (None, tgt)):
@@ -1165,15 +1378,18 @@ def _emit_body(ins, n_consts, n_slots, mem_ops, mem_index, D, fused, out_macro, 
                     emit("    qg_dot_zero(wd);")
                     wide["acc"] = tgt
                 emit("    qg_dot_mad(wd, %s, %s);" % (v, src))
+                if kind == SRC_TALPHA and ALPHA_PIN:               # (the factor is a register, not an LDS read: nothing else keeps the
+                    emit("    QG_PIN_WIDE(wd)")                    #  81 multiply-adds here - see quotient_gen.h)
                 wide["terms"] += bound[d]
                 stats["fused"] += 1
+                stats["alpha_terms"] += kind == SRC_TALPHA
                 skip_add.add(pc + 1)
             elif src_acc == d:                                 # v * v: the square routine wants a normalised value
                 if bound[d] > 1:
                     reduce_acc(d)
                 emit("    %s = fl_sqr(%s);" % (v, v))
                 bound[d] = 1
-            elif kind == SRC_CONST:
+            elif kind in (SRC_CONST, SRC_TALPHA):                 # (an alpha copy is canonical and carries its 2^24, like a scaled table)
                 emit("    %s = fl_mul_r280(%s, %s);" % (v, v, src))
                 stats["mulr"] += 1
                 bound[d] = 1
@@ -1280,9 +1496,10 @@ QGenPart quotient_gen_%(layout)s%(suffix)s_p%(part)d() { return QGenPart{%(wgs)d
         f.write(src)
 
 
-def write_kernel_table(layout, suffix, variant, code, n_consts, n_tables, ncols, n_parts, scaled=(), derived=(), baked=()):
+def write_kernel_table(layout, suffix, variant, code, n_consts, n_tables, ncols, n_parts, scaled=(), derived=(), baked=(), alpha=()):
     """the host-side entry of one variant: what ss_eval_quotient looks up by the program's hash.  `baked`: (constant, Montgomery image)
-    of every constant some part multiplies by with shifts and adds - the launch compares them with the program's constant table"""
+    of every constant some part multiplies by with shifts and adds - the launch compares them with the program's constant table.
+    `alpha`: the alpha copies (table, constant, form) the parts read through QG_TABLE_ALPHA_RAW, in the bodies' numbering"""
     decl = "".join("QGenPart quotient_gen_%s%s_p%d();\n" % (layout, suffix, j) for j in range(n_parts))
     parts = ", ".join("quotient_gen_%s%s_p%d()" % (layout, suffix, j) for j in range(n_parts))
     src = """// GENERATED by tools/gen_quotient.py - DO NOT EDIT; regenerate with `python tools/gen_quotient.py %(layout)s`.
@@ -1303,14 +1520,18 @@ const QGenKernel &quotient_gen_%(layout)s%(suffix)s() {
     // constants the kernels hold as code (small structural multiples: tools/gen_quotient.py structural_constants): constant index and the
     // interchange image it must have - ss_eval_quotient interprets a program whose table says otherwise
     static const QGenBaked baked[] = {%(baked)s};
+    // alpha copies the kernels read (tools/gen_quotient.py fold_alpha_tables; made per launch behind the scaled tables): copy j is table
+    // `table` times constant `constant` in form 0 (R280: times 2^24), 1 (R280_UP: times 2^48) or 2 (R280_UPN: times -2^48)
+    static const QGenAlpha alpha[] = {%(alpha)s};
     static const QGenKernel k = {"%(layout)s", 0x%(hash)016xull, %(n_instr)du, %(n_consts)du, %(n_tables)du, %(ncols)du, %(variant)du, %(n_parts)du, {%(parts)s},
-                                 %(n_baked)du, baked, %(n_scaled)du, scaled, %(n_derived)du, {%(derived)s}};
+                                 %(n_baked)du, baked, %(n_alpha)du, alpha, %(n_scaled)du, scaled, %(n_derived)du, {%(derived)s}};
     return k;
 }
 
 }  // namespace ss
 """ % dict(layout=layout, suffix=suffix, variant=variant, n_parts=n_parts, hash=code_hash(code), n_instr=len(code) // 2, n_consts=n_consts,
            n_tables=n_tables, ncols=ncols, decl=decl, parts=parts, n_scaled=len(scaled), scaled=", ".join("%du" % t for t in scaled) if scaled else "0u", n_derived=len(derived), n_baked=len(baked),
+           n_alpha=len(alpha), alpha=", ".join("{%du, %du, %du}" % a for a in alpha) if alpha else "{0u, 0u, 0u}",
            baked=", ".join("{%du, {%s}}" % (c, ", ".join("0x%016xull" % ((v >> (64 * j)) & (2**64 - 1)) for j in range(4))) for c, v in baked) if baked else "{0u, {0, 0, 0, 0}}",
            derived=", ".join("{%du, %du, {%s}, {%s}}" % (col, len(terms), ", ".join("%du" % off for off, _ in terms), ", ".join("%d" % c for _, c in terms))
                              for col, terms in derived))
@@ -1321,6 +1542,9 @@ const QGenKernel &quotient_gen_%(layout)s%(suffix)s() {
             f.write("// GENERATED by tools/gen_quotient.py - DO NOT EDIT.  Tables the `%s` kernels read from a copy times 2^24.\n"
                     "static const uint32_t QG_N_TABLES = %du, QG_N_SCALED = %du;\nstatic const uint32_t QG_SCALED_TABLES[] = {%s};\n"
                     % (layout, n_tables, len(scaled), ", ".join("%du" % t for t in scaled) if scaled else "0u"))
+            f.write("// ... and the alpha copies, in the bodies' numbering: {table, constant, form (0 R280, 1 R280_UP, 2 R280_UPN)}\n"
+                    "static const uint32_t QG_N_ALPHA = %du;\nstatic const uint32_t QG_ALPHA_COPIES[][3] = {%s};\n"
+                    % (len(alpha), ", ".join("{%du, %du, %du}" % a for a in alpha) if alpha else "{0u, 0u, 0u}"))
 
 
 def write_source_lists(written, all_variants):
