@@ -378,6 +378,14 @@ ss_status ss_ntt_gl64(ss_ctx *ctx, uint64_t *const *d_cols, uint32_t ncols, uint
                       int in_order, int out_order);
 ss_status ss_lde_gl64(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols, uint32_t log_n, uint32_t log_blowup,
                       uint64_t offset, uint64_t *const *d_evals, uint64_t *const *d_coeffs /* nullable; bit-reversed */);
+/* ss_subsample_rows over one-word cells: d_out[c][j] = d_in[c][j << log_stride], j < nrows_out.  With log_blowup above 1 the plain
+ * AIR's constraints (degree 2) are still evaluated on the 2n-point coset offset*<w_2n> only: rows j << (log_blowup - 1) of the LDE,
+ * which this call hands to ss_eval_quotient_gl64x3 as columns of log_blowup = 1.  A bit-exact copy of 64-bit words: nothing is
+ * reduced, words >= p pass through.  d_in[c] holds at least ((nrows_out - 1) << log_stride) + 1 words, d_out[c] nrows_out, and nothing
+ * beyond them is written; the two do not overlap.  nrows_out > 0; log_stride <= 4; any ncols (16 columns a launch).  On the ctx
+ * stream, no host sync. */
+ss_status ss_subsample_rows_gl64(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride,
+                                 uint64_t *const *d_out);
 /* one FRI layer over Fq3-valued evaluations (interleaved [2^log_len][3]) on the Fp domain domain_offset * <w>, natural
  * order: row j = {evals[j + k len/fold]}, d_out[j] = (degree < fold interpolant of row j)(alpha), alpha in Fq3;
  * flags: SS_FRI_UNNORMALISED multiplies by fold */
@@ -414,8 +422,10 @@ ss_status ss_gather_rows_gl64(ss_ctx *ctx, const uint64_t *const *d_segments, ui
                               const uint64_t *idx, uint32_t nidx, uint64_t *out);
 /* Q1 over the cubic extension: the program format of ss_eval_quotient (ss_air_program above) with accumulators, scratch
  * slots and constants in Fq3 - prog->consts holds n_consts x 3 values < p - and trace cells, tables (prog->d_tables: 8-byte
- * elements) and x in Fp, read into the first coordinate.  d_out: [n * blowup][3] interleaved.  Interpreted (no compiled
- * kernel for this field's experimental layout). */
+ * elements) and x in Fp, read into the first coordinate, x_i = offset * w^i over the 2^(log_n + log_blowup)-point coset the columns
+ * and the tables are laid out on.  d_out: [2^(log_n + log_blowup)][3] interleaved.  The plain layout's program runs as a compiled
+ * kernel (csrc/quotient_gen_plain_gl.inc, recognised by its code), any other through the interpreter.  The provers call it with
+ * log_blowup = 1 whatever the LDE's blowup is (ss_subsample_rows_gl64 hands it the coset's rows). */
 ss_status ss_eval_quotient_gl64x3(ss_ctx *ctx, const ss_air_program *prog, const uint64_t *const *d_lde_cols, uint32_t ncols,
                                   uint32_t log_n, uint32_t log_blowup, uint64_t offset, uint64_t *d_out);
 /* ss_check_constraints over the cubic extension: the check program's format, domains and results are ss_check_constraints' (one

@@ -158,6 +158,7 @@ SIGNATURES = {
                                   C.c_void_p, _u64p, C.c_void_p]),
     "ss_ntt_gl64": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_int, C.c_int]),
     "ss_lde_gl64": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vpp, _vpp]),
+    "ss_subsample_rows_gl64": (C.c_int, [C.c_void_p, _vpp, C.c_uint32, C.c_uint64, C.c_uint32, _vpp]),
     "ss_fri_fold_gl64x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _u64p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "ss_running_product_gl64x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, _u64p, _u64p, _vpp,
                                             C.c_uint64, C.c_uint64, _u64p]),

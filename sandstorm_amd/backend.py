@@ -253,6 +253,11 @@ class Context:
         check(self.lib.ss_lde_gl64(self.handle, _ptr_array(cols_in), len(cols_in), log_n, log_blowup, int(offset),
                                    _ptr_array(evals_out), _ptr_array(coeffs_out) if coeffs_out else None))
 
+    def subsample_rows_gl64(self, cols_in, nrows_out, log_stride, cols_out):
+        """ss_subsample_rows_gl64: cols_out[c][j] = cols_in[c][j << log_stride], j < nrows_out, over 8-byte words copied as they are (the
+        constraint-evaluation coset's rows of a wider LDE)"""
+        check(self.lib.ss_subsample_rows_gl64(self.handle, _ptr_array(cols_in), len(cols_in), nrows_out, log_stride, _ptr_array(cols_out)))
+
     def fri_fold_gl64x3(self, evals, log_len, fold, alpha, offset, out, flags=0):
         a = np.ascontiguousarray(alpha, dtype=np.uint64)
         check(self.lib.ss_fri_fold_gl64x3(self.handle, _ptr_of(evals), log_len, fold, a.ctypes.data_as(C.POINTER(C.c_uint64)), int(offset),

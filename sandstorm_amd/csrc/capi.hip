@@ -2964,6 +2964,21 @@ ss_status ss_lde_gl64(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols, 
     return SS_OK;
 }
 
+// ss_subsample_rows over one-word cells (include/sandstorm_hip.h): MAX_COLS columns per launch, no host sync.
+ss_status ss_subsample_rows_gl64(ss_ctx *ctx, const uint64_t *const *d_in, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride,
+                                 uint64_t *const *d_out) {
+    if (!ctx || !d_in || !d_out) return fail(SS_ERR_INVALID, "NULL argument");
+    if (!ncols || !nrows_out) return fail(SS_ERR_INVALID, "no columns or no rows");
+    if (log_stride > 4) return fail(SS_ERR_INVALID, "log_stride %u > 4", log_stride);
+    if (nrows_out > (1ull << 40)) return fail(SS_ERR_INVALID, "size out of range");
+    if (has_null((const void *const *)d_in, ncols) || has_null((const void *const *)d_out, ncols)) return fail(SS_ERR_INVALID, "NULL column");
+    for (uint32_t base = 0; base < ncols; base += MAX_COLS) {
+        const uint32_t nc = ncols - base < (uint32_t)MAX_COLS ? ncols - base : (uint32_t)MAX_COLS;
+        HIP_TRY(launch_gl_subsample_rows(ctx->stream, d_in + base, d_out + base, nc, nrows_out, log_stride));
+    }
+    return SS_OK;
+}
+
 // Fq3 arithmetic on the host (coefficients, constants): Fp[X] / (X^3 - 2)
 struct HGl3 { uint64_t c[3]; };
 static uint64_t gl_addh(uint64_t a, uint64_t b) { const uint64_t s = a + b; return (s < a || s >= GL_P) ? s - GL_P : s; }

@@ -81,6 +81,38 @@ __global__ void gl_bitrev_copy_kernel(const uint64_t *__restrict__ src, uint64_t
         dst[__brevll(i) >> (64u - log_n)] = src[i];
 }
 
+// ---- row sub-sampling: dst[c][j] = src[c][j << log_stride], j < nrows_out (the constraint-evaluation coset's rows out of a wider
+// LDE's: ss_subsample_rows_gl64).  Words are copied as they are - nothing is reduced.  One lane two adjacent output cells: two 8-byte
+// loads (32 << log_stride bytes apart across the wave: 8 of every 8 << log_stride bytes are used) and ONE 16-byte store, so a wave
+// writes 1 KiB contiguously; an odd nrows_out leaves one cell to lane 0 of the first workgroup.  A destination that is not 16-byte
+// aligned (a view into a larger buffer) takes 8-byte stores, still contiguous across the wave.
+__global__ __launch_bounds__(256) void gl_subsample_rows_kernel(GlCols cols, uint64_t nrows_out, uint32_t log_stride) {
+    const uint64_t *src = cols.src[0];
+    uint64_t *dst = cols.dst[0];
+#pragma unroll
+    for (int c = 1; c < MAX_COLS; ++c)
+        if (blockIdx.y == (unsigned)c) { src = cols.src[c]; dst = cols.dst[c]; }
+    const uint64_t first = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        const uint64_t pairs = nrows_out >> 1;
+        for (uint64_t j = first; j < pairs; j += step)
+            *reinterpret_cast<ulonglong2 *>(dst + 2 * j) = make_ulonglong2(src[(2 * j) << log_stride], src[(2 * j + 1) << log_stride]);
+        if ((nrows_out & 1) && first == 0) dst[nrows_out - 1] = src[(nrows_out - 1) << log_stride];
+    } else {
+        for (uint64_t j = first; j < nrows_out; j += step) dst[j] = src[j << log_stride];
+    }
+}
+hipError_t launch_gl_subsample_rows(hipStream_t st, const uint64_t *const *src, uint64_t *const *dst, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride) {
+    if (nrows_out == 0 || ncols == 0) return hipSuccess;
+    if (ncols > (uint32_t)MAX_COLS) return hipErrorInvalidValue;
+    GlCols cols;
+    for (int c = 0; c < MAX_COLS; ++c) { cols.src[c] = c < (int)ncols ? src[c] : nullptr; cols.dst[c] = c < (int)ncols ? dst[c] : nullptr; }
+    uint64_t gx = ((nrows_out + 1) / 2 + 255) / 256;
+    if (gx > 65536) gx = 65536;
+    hipLaunchKernelGGL(gl_subsample_rows_kernel, dim3((uint32_t)gx, ncols), dim3(256), 0, st, cols, nrows_out, log_stride);
+    return hipGetLastError();
+}
+
 // ---- Fq3 = Fp[X] / (X^3 - 2) and one FRI layer over Fq3-valued evaluations ------------------------------------------
 struct Gl3FriConsts {
     uint64_t winv[16];           // w_fold^-k

@@ -271,6 +271,8 @@ hipError_t launch_gl_ntt_pass(hipStream_t st, bool dif, const void *const *src, 
                               uint64_t scale);
 hipError_t launch_gl_twiddles(hipStream_t st, uint64_t *tw, const uint64_t *pow_lo, const uint64_t *pow_hi, const uint64_t *hpow, uint32_t log_n);
 hipError_t launch_gl_bitrev_copy(hipStream_t st, const uint64_t *src, uint64_t *dst, uint32_t log_n);
+// dst[c][j] = src[c][j << log_stride], j < nrows_out, c < ncols <= MAX_COLS: 8-byte words copied as they are
+hipError_t launch_gl_subsample_rows(hipStream_t st, const uint64_t *const *src, uint64_t *const *dst, uint32_t ncols, uint64_t nrows_out, uint32_t log_stride);
 hipError_t launch_gl3_fri_fold(hipStream_t st, const uint64_t *evals, uint32_t log_len, uint32_t fold, const uint64_t alpha[3], uint64_t offset,
                                bool unnormalised, uint64_t *out);
 hipError_t launch_gl3_inverse_table(hipStream_t st, uint64_t *D, uint64_t len, uint64_t x0, uint64_t w, const uint64_t z[3]);

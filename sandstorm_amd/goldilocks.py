@@ -184,6 +184,13 @@ def fri_geometry(n_lde, opt: Options):
         raise ValueError("FRI geometry refused: %s %s" % (e, nums))
 
 
+def check_log_blowup(log_blowup):
+    """the LDE blowups the provers and the verifier take: 2, 4, 8 and 16.  A ValueError naming the option otherwise - asked, like
+    fri_geometry, before anything is uploaded or launched (host/goldilocks_prover.cpp check_log_blowup words it the same way)"""
+    if isinstance(log_blowup, bool) or not isinstance(log_blowup, (int, np.integer)) or not 1 <= log_blowup <= 4:
+        raise ValueError("log_blowup refused: the log blowup must be 1, 2, 3 or 4 (LDE blowup 2, 4, 8 or 16), not %r" % (log_blowup,))
+
+
 def _powers3(a, count):
     out, cur = [], (1, 0, 0)
     for _ in range(count):
@@ -249,15 +256,47 @@ class Prover:
         paths, _ = self.ctx.merkle_open(nodes, None, n_rows, positions)
         return Opening(rows, paths)
 
+    def composition_columns(self, trace_ev, log_n, prog, d_tables, tdesc):
+        """steps 3-4 of prove(): the lowered program `prog` (tables `d_tables` / `tdesc` of make_tables(n, 1)) over the trace LDE columns
+        `trace_ev` (N = n << log_blowup rows each) -> (comp_co, comp_ev): H0's then H1's coordinate columns, H(x) = H0(x^2) + x H1(x^2), as
+        n bit-reversed coefficients each and as N evaluations each.  The constraints have degree 2, so whatever the blowup they are
+        evaluated on the 2n-point coset OFFSET * <w_2n> only: every 2^(lb-1)-th row of the LDE (the LDE itself at lb = 1, copied out
+        by ss_subsample_rows_gl64 above it)"""
+        import torch
+        ctx, lb = self.ctx, self.opt.log_blowup
+        n = 1 << log_n
+        N, dev = n << lb, trace_ev[0].device
+        if lb == 1:
+            ce = trace_ev
+        else:
+            ce = [torch.empty(2 * n, dtype=torch.int64, device=dev) for _ in trace_ev]          # fully written by the kernel
+            ctx.subsample_rows_gl64(trace_ev, 2 * n, lb - 1, ce)
+        q = torch.empty((2 * n, 3), dtype=torch.int64, device=dev)
+        ctx.eval_quotient_gl64x3(np.array(prog.code, dtype=np.uint32), np.array(prog.consts, dtype=np.uint64).reshape(-1, 3), prog.n_slots,
+                                 d_tables, tdesc, ce, log_n, 1, OFFSET, q)
+        ce = None                                                                        # the 2n-row copies go before the commitment
+        comp_co, comp_ev = [], []
+        qc = [q[:, t].contiguous() for t in range(3)]
+        ctx.ntt_gl64(qc, log_n + 1, be.INVERSE, OFFSET, be.NATURAL, be.BITREV)         # bit-reversed coefficients: even ones first
+        for half in range(2):
+            for t in range(3):
+                comp_co.append(qc[t][half * n:(half + 1) * n].contiguous())
+        for c in comp_co:
+            padded = torch.zeros(N, dtype=torch.int64, device=dev)
+            padded[::1 << lb] = c                                                    # zero-padded to N in bit-reversed order
+            ctx.ntt_gl64([padded], log_n + lb, be.FORWARD, OFFSET, be.BITREV, be.NATURAL)
+            comp_ev.append(padded)
+        return comp_co, comp_ev
+
     def prove(self, seed: bytes, base_cols, build_extension, tables=None, statement=None, validate=None):
         """base_cols: the base columns [n] (device); build_extension(challenges) -> the extension trace's coordinate columns.
-        statement: passed through to air.composition (hints come from it).  validate: this call's override of the prover's switch"""
+        statement: passed through to air.composition (hints come from it).  validate: this call's override of the prover's switch.
+        tables: the AIR's, over the constraint-evaluation coset (make_tables(n, 1)) whatever Options.log_blowup is"""
         import torch
         ctx, air, opt = self.ctx, self.air, self.opt
         n = base_cols[0].shape[0]
         log_n, lb = n.bit_length() - 1, opt.log_blowup
-        if lb != 1:
-            raise ValueError("the composition split (even / odd coefficients) is written for blowup 2")
+        check_log_blowup(lb)
         N = n << lb
         fri_geometry(N, opt)                        # refused here, not at step 7 after every commitment
         dev = base_cols[0].device
@@ -284,27 +323,14 @@ class Prover:
             proof.ext_root, ext_nodes = self._commit(ext_ev, N)
             coin.reseed_with_digest(proof.ext_root)
         trace_ev, trace_co = base_ev + ext_ev, base_co + ext_co
-        # 3-4. composition: the lowered program over the LDE domain, then H = H0(x^2) + x H1(x^2) as six coordinate columns
+        # 3-4. composition: the lowered program over the 2n-point coset, then H = H0(x^2) + x H1(x^2) as six coordinate columns
         alpha = coin.draw_fq3()
-        tables = tables or air.make_tables(n, lb)
+        tables = tables or air.make_tables(n, 1)
         root = air.composition(n, challenges, alpha, tables, statement)
         prog = ap.lower(root, P, ext=True, symbols=tables.symbols)
         tvals, tdesc = tables.device_tables()
         d_tables = torch.from_numpy(tvals.view(np.int64)).to(dev)
-        q = new(N, 3)
-        ctx.eval_quotient_gl64x3(np.array(prog.code, dtype=np.uint32), np.array(prog.consts, dtype=np.uint64).reshape(-1, 3), prog.n_slots,
-                                 d_tables, tdesc, trace_ev, log_n, lb, OFFSET, q)
-        comp_co, comp_ev = [], []
-        qc = [q[:, t].contiguous() for t in range(3)]
-        ctx.ntt_gl64(qc, log_n + lb, be.INVERSE, OFFSET, be.NATURAL, be.BITREV)       # bit-reversed coefficients: even ones first
-        for half in range(2):
-            for t in range(3):
-                comp_co.append(qc[t][half * n:(half + 1) * n].contiguous())
-        for c in comp_co:
-            padded = torch.zeros(N, dtype=torch.int64, device=dev)
-            padded[::1 << lb] = c                                                    # zero-padded to N in bit-reversed order
-            ctx.ntt_gl64([padded], log_n + lb, be.FORWARD, OFFSET, be.BITREV, be.NATURAL)
-            comp_ev.append(padded)
+        comp_co, comp_ev = self.composition_columns(trace_ev, log_n, prog, d_tables, tdesc)
         proof.comp_root, comp_nodes = self._commit(comp_ev, N)
         coin.reseed_with_digest(proof.comp_root)
         # 5. out-of-domain evaluations
@@ -470,6 +496,7 @@ def _verify(proof, air, seed, statement, expected_options, required_security_bit
               (opt.num_queries, opt.log_blowup, opt.grinding, opt.fold, opt.max_remainder, proof.trace_len, proof.pow_nonce)), "options: not integers")
     if expected_options is not None:
         _need(opt == expected_options, "options are not the expected ones")
+    _need(1 <= opt.log_blowup <= 4, "options: log_blowup must be 1, 2, 3 or 4 (LDE blowup 2, 4, 8 or 16), not %r" % (opt.log_blowup,))
     _need(1 <= opt.num_queries <= 256 and opt.fold in (2, 4, 8, 16) and 1 <= opt.log_blowup <= 4 and 1 <= opt.max_remainder <= 1 << 16
           and 0 <= opt.grinding <= 40, "options out of range")
     n = int(proof.trace_len)
@@ -479,7 +506,6 @@ def _verify(proof, air, seed, statement, expected_options, required_security_bit
     _need(sec >= required_security_bits, "the proof's options conjecture %d bits of security, %d required" % (sec, required_security_bits))
     log_n, lb = n.bit_length() - 1, opt.log_blowup
     N = n << lb
-    _need(lb == 1, "the composition split is written for blowup 2")
     _need(all(isinstance(r, (bytes, bytearray)) and len(r) == 32 for r in [proof.base_root, proof.comp_root] + ([proof.ext_root] if air.num_ext else [])),
           "roots: 32 bytes each")
     _u64_array(proof.ood_trace, (len(air.mask), 3), "out-of-domain trace values")
@@ -501,7 +527,7 @@ def _verify(proof, air, seed, statement, expected_options, required_security_bit
     ood_c = [tuple(int(v) for v in r) for r in proof.ood_comp]
     _need(all(c < P for v in list(ood_t.values()) + ood_c for c in v), "out-of-domain values: range")
     # the AIR identity at z: sum_k alpha^k C_k(z) multiplier_k(z) = H0(z^2) + z H1(z^2), H_h = sum_t X^t comp[3 h + t]
-    tables = air.make_tables(n, lb)
+    tables = air.make_tables(n, 1)                     # value_at does not read the coset; the provers' tables are this one's at every blowup
     root = air.composition(n, challenges, alpha, tables, statement)
     g = F.root_of_unity(log_n)
     lhs = ap.evaluate_ext(root, P, z, lambda c, o: ood_t[(c, o)], lambda t: tables.value_at(tables.specs[t], z), symbols=tables.symbols)

@@ -193,12 +193,16 @@ FriShape fri_shape(const Options &opt, uint64_t n_lde) {
     }
     return s;
 }
+void check_log_blowup(uint32_t log_blowup) {
+    if (log_blowup < 1 || log_blowup > 4)
+        throw std::runtime_error("log_blowup refused: the log blowup must be 1, 2, 3 or 4 (LDE blowup 2, 4, 8 or 16), not " + std::to_string(log_blowup));
+}
 
 Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &statement_digest, const std::vector<const uint64_t *> &base_cols,
             uint64_t n, const std::vector<std::pair<uint32_t, uint32_t>> &mask, uint32_t num_challenges, uint32_t num_ext,
             const ExtensionBuilder &build_extension, const ProgramBuilder &build_program, const CheckBuilder &build_check) {
     if (!n || (n & (n - 1))) throw std::runtime_error("trace length: a power of two");
-    if (opt.log_blowup != 1) throw std::runtime_error("the composition split (even / odd coefficients) is written for blowup 2");
+    check_log_blowup(opt.log_blowup);
     uint32_t log_n = 0;
     while ((1ull << log_n) < n) ++log_n;
     const uint32_t lb = opt.log_blowup;
@@ -270,7 +274,7 @@ Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &s
         const std::vector<ConstraintFailure> bad = check_trace(ctx, build_check(challenges), base_cols, log_n);
         if (!bad.empty()) throw std::runtime_error(describe_failures(bad));
     }
-    // 3-4. composition: the lowered program over the LDE domain, then H = H0(x^2) + x H1(x^2) as six coordinate columns
+    // 3-4. composition: the lowered program over the 2n-point coset, then H = H0(x^2) + x H1(x^2) as six coordinate columns
     const Fq3 alpha = coin.draw_fq3();
     const ProgramData pd = build_program(challenges, alpha);
     ss_air_program prog;
@@ -283,17 +287,34 @@ Proof prove(ss_ctx *ctx, const Options &opt, const Digest &seed, const Digest &s
     prog.n_slots = pd.n_slots;
     std::vector<const uint64_t *> comp_co, comp_ev;
     {
-        Dev q(ctx, 24 * N);
-        ok(ss_eval_quotient_gl64x3(ctx, &prog, trace_ev.data(), (uint32_t)trace_ev.size(), log_n, lb, OFFSET, q.u64()));
+        // The constraints have degree 2: whatever the blowup they are evaluated on the 2n-point coset OFFSET * <w_2n> only - every
+        // 2^(lb-1)-th row of the LDE, the LDE itself at lb = 1 and copied out as columns of their own above it (freed with this block's
+        // first half, before the composition commitment); the program's tables are those of that coset
+        const uint64_t n2 = 2 * n;
+        Dev q(ctx, 24 * n2);
+        {
+            std::vector<DevP> ce_buf;
+            std::vector<const uint64_t *> ce_cols = trace_ev;
+            if (lb > 1) {
+                std::vector<uint64_t *> ce_out;
+                for (size_t c = 0; c < trace_ev.size(); ++c) {
+                    ce_buf.emplace_back(new Dev(ctx, 8 * n2));
+                    ce_out.push_back(ce_buf.back()->u64());
+                    ce_cols[c] = ce_buf.back()->u64();
+                }
+                ok(ss_subsample_rows_gl64(ctx, trace_ev.data(), (uint32_t)trace_ev.size(), n2, lb - 1, ce_out.data()));
+            }
+            ok(ss_eval_quotient_gl64x3(ctx, &prog, ce_cols.data(), (uint32_t)ce_cols.size(), log_n, 1, OFFSET, q.u64()));
+        }
         // de-interleave the three coordinates, interpolate each over the coset (bit-reversed coefficients: the even ones first)
         std::vector<uint64_t *> qc;
         std::vector<DevP> qbuf;
         for (int t = 0; t < 3; ++t) {
-            qbuf.emplace_back(new Dev(ctx, 8 * N));
+            qbuf.emplace_back(new Dev(ctx, 8 * n2));
             qc.push_back(qbuf.back()->u64());
-            ok(ss_dev_copy_2d(ctx, qc[t], 8, q.u8() + 8 * t, 24, 8, N));
+            ok(ss_dev_copy_2d(ctx, qc[t], 8, q.u8() + 8 * t, 24, 8, n2));
         }
-        ok(ss_ntt_gl64(ctx, qc.data(), 3, log_n + lb, SS_NTT_INVERSE, OFFSET, SS_ORDER_NATURAL, SS_ORDER_BITREV));
+        ok(ss_ntt_gl64(ctx, qc.data(), 3, log_n + 1, SS_NTT_INVERSE, OFFSET, SS_ORDER_NATURAL, SS_ORDER_BITREV));
         for (int half = 0; half < 2; ++half)
             for (int t = 0; t < 3; ++t) {
                 keep.emplace_back(new Dev(ctx, 8 * n));

@@ -29,6 +29,9 @@ struct Options {                                            // goldilocks.py Opt
 // the rule and the numbers.
 struct FriShape { uint32_t layers; uint64_t last_len; };
 FriShape fri_shape(const Options &opt, uint64_t n_lde);
+// The LDE blowups prove() takes: log_blowup 1 .. 4.  Throws naming the option otherwise (goldilocks.py check_log_blowup's words); asked
+// with fri_shape, before anything is uploaded or launched.
+void check_log_blowup(uint32_t log_blowup);
 struct Opening {
     uint32_t width = 0, depth = 0;
     std::vector<uint64_t> rows;                             // [positions][width]

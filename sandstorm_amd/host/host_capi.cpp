@@ -1001,8 +1001,9 @@ int ssh_gl_prove_files_device_checked(ss_ctx *ctx, const uint8_t *trace_bin, uin
         {                                                            // a FRI geometry gl::prove would refuse: before the files go up
             gl::Options opt;
             opt.log_blowup = options[1]; opt.fold = options[3]; opt.max_remainder = options[4];
-            // (a cycle count or a blowup that is refused anyway keeps the message it has: the trace plan's, gl::prove's)
-            if (opt.log_blowup == 1 && n_steps && !(n_steps & (n_steps - 1)) && n_steps <= (1ull << 28)) gl::fri_shape(opt, (16 * n_steps) << opt.log_blowup);
+            // (a cycle count that is refused anyway keeps the message it has: the trace plan's)
+            gl::check_log_blowup(opt.log_blowup);
+            if (n_steps && !(n_steps & (n_steps - 1)) && n_steps <= (1ull << 28)) gl::fri_shape(opt, (16 * n_steps) << opt.log_blowup);
         }
         plain_base_trace_device(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols);
         const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();

@@ -684,7 +684,7 @@ def gl_prove(ctx, air, options, seed, base_cols, build_extension, tables=None, s
     from . import goldilocks as gs
     opt = options or gs.Options()
     n = int(base_cols[0].shape[0]) if hasattr(base_cols[0], "shape") else int(base_cols[0].nbytes // 8)
-    tables = tables or air.make_tables(n, opt.log_blowup)
+    tables = tables or air.make_tables(n, 1)           # the constraint-evaluation coset's (2n points), whatever the LDE's blowup is
     keep = []
 
     def ext_cb(_user, ch_ptr, nch, out_ptr):
@@ -807,7 +807,7 @@ def gl_prove_files(ctx, air, options, seed, trace_bin: bytes, memory_bin: bytes,
     if len(dev_cols) != 5:
         raise _lib.SandstormHipError("host: %d device columns for a layout of 5" % len(dev_cols))
     n = 16 * (len(trace_bin) // 24)
-    tables = tables or air.make_tables(n, opt.log_blowup)
+    tables = tables or air.make_tables(n, 1)           # the constraint-evaluation coset's (2n points), whatever the LDE's blowup is
     keep = []
     args, keep_args = _gl_files_args(trace_bin, memory_bin, pi)
     fn = load().ssh_gl_prove_files_device
