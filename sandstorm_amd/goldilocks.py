@@ -647,10 +647,12 @@ def plain_base_trace_on_device(ctx, trace_bin, memory_bin, pi, out=None):
     return out
 
 
-def prove_files(ctx, trace_bin, memory_bin, pi, seed, options=None, out=None, want_times=False, validate=False):
+def prove_files(ctx, trace_bin, memory_bin, pi, seed, options=None, out=None, want_times=False, validate=False, lowering="python", air=None):
     """the claim from the files in ONE call, what the reference's "Proof generated in" timer wraps (cli/src/main.rs:186-202): the base
-    columns made on the device, the extension column built and the proof written by the C++ host (hostlib.gl_prove_files); only the
-    plain AIR's lowering comes from Python.  -> the Proof Prover.prove writes from base_trace's columns with the same seed and statement
+    columns made on the device, the extension column built and the proof written by the C++ host (hostlib.gl_prove_files).
+    lowering: where the plain AIR is lowered - "python" (air_program.lower per proof, through the C++ host's program callback) or "host"
+    (host/air_plain.cpp: hostlib.gl_prove_files_air, no callback of any kind; `air`: a hostlib.GlPlainAir made for `ctx` and `pi` to reuse,
+    else one is made for the call).  -> the Proof Prover.prove writes from base_trace's columns with the same seed and statement
     (with want_times: (Proof, {"trace_gen_s", "total_s"})).  validate: the C++ host checks the trace against the AIR before the extension
     commitment (check_trace's report, Prover's message, raised as SandstormHipError)"""
     import torch
@@ -659,7 +661,18 @@ def prove_files(ctx, trace_bin, memory_bin, pi, seed, options=None, out=None, wa
     if out is None:
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         out = [torch.empty(n, dtype=torch.int64, device=dev) for _ in range(F.NUM_BASE_COLUMNS)]
-    proof, times = hostlib.gl_prove_files(ctx, plain_air(), options or Options(), seed, trace_bin, memory_bin, pi, out, validate=validate)
+    if lowering == "host":
+        own = air is None
+        air = hostlib.GlPlainAir(ctx, pi) if own else air
+        try:
+            proof, times = hostlib.gl_prove_files_air(ctx, air, options or Options(), seed, trace_bin, memory_bin, out, validate=validate)
+        finally:
+            if own:
+                air.close()
+    elif lowering == "python":
+        proof, times = hostlib.gl_prove_files(ctx, plain_air(), options or Options(), seed, trace_bin, memory_bin, pi, out, validate=validate)
+    else:
+        raise ValueError("lowering: 'python' or 'host', not %r" % (lowering,))
     return (proof, times) if want_times else proof
 
 

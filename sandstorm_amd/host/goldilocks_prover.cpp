@@ -6,6 +6,7 @@
 // points); what the layout decides - the extension columns, the lowered composition program for the drawn challenges - comes
 // from the caller through two callbacks, as the 252-bit Prover takes its extension builder.
 #include "goldilocks_prover.hpp"
+#include "gl_transcript.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -24,117 +25,8 @@ static uint64_t mulm(uint64_t a, uint64_t b) { return (uint64_t)((unsigned __int
 static uint64_t addm(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a + b) % P); }
 static uint64_t powm(uint64_t a, uint64_t e) { uint64_t r = 1; for (; e; e >>= 1) { if (e & 1) r = mulm(r, a); a = mulm(a, a); } return r; }
 static uint64_t invm(uint64_t a) { return powm(a, P - 2); }
-Fq3 mul3(const Fq3 &a, const Fq3 &b) {                     // X^3 = 2
-    const uint64_t d0 = mulm(a[0], b[0]), d1 = addm(mulm(a[0], b[1]), mulm(a[1], b[0]));
-    const uint64_t d2 = addm(addm(mulm(a[0], b[2]), mulm(a[1], b[1])), mulm(a[2], b[0]));
-    const uint64_t d3 = addm(mulm(a[1], b[2]), mulm(a[2], b[1])), d4 = mulm(a[2], b[2]);
-    return Fq3{addm(d0, addm(d3, d3)), addm(d1, addm(d4, d4)), d2};
-}
 static Fq3 pow3(Fq3 a, uint64_t e) { Fq3 r{1, 0, 0}; for (; e; e >>= 1) { if (e & 1) r = mul3(r, a); a = mul3(a, a); } return r; }
-
-// ---- SHA-256 (FIPS 180-4) for the coin's host side; the trees' SHA-256 is the device's (csrc/hash.hip)
-static uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-Digest sha256(const uint8_t *msg, size_t len) {
-    static const uint32_t K[64] = {
-        0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u,
-        0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-        0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u,
-        0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u, 0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-        0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
-        0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-    uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-    std::vector<uint8_t> m(msg, msg + len);
-    m.push_back(0x80);
-    while (m.size() % 64 != 56) m.push_back(0);
-    for (int i = 7; i >= 0; --i) m.push_back((uint8_t)(((uint64_t)len * 8) >> (8 * i)));
-    for (size_t off = 0; off < m.size(); off += 64) {
-        uint32_t w[64];
-        for (int t = 0; t < 16; ++t) w[t] = ((uint32_t)m[off + 4 * t] << 24) | ((uint32_t)m[off + 4 * t + 1] << 16) | ((uint32_t)m[off + 4 * t + 2] << 8) | m[off + 4 * t + 3];
-        for (int t = 16; t < 64; ++t)
-            w[t] = w[t - 16] + (rotr(w[t - 15], 7) ^ rotr(w[t - 15], 18) ^ (w[t - 15] >> 3)) + w[t - 7] + (rotr(w[t - 2], 17) ^ rotr(w[t - 2], 19) ^ (w[t - 2] >> 10));
-        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-        for (int t = 0; t < 64; ++t) {
-            const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K[t] + w[t];
-            const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-            hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-        }
-        h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-    }
-    Digest out;
-    for (int i = 0; i < 8; ++i) { out[4 * i] = (uint8_t)(h[i] >> 24); out[4 * i + 1] = (uint8_t)(h[i] >> 16); out[4 * i + 2] = (uint8_t)(h[i] >> 8); out[4 * i + 3] = (uint8_t)h[i]; }
-    return out;
-}
-
-// ---- the coin (goldilocks.py Coin over coin.PublicCoin's Solidity shape: solidity.rs:54-118 with H = Keccak-256 or SHA-256)
-namespace {
-struct Coin {
-    Digest digest;
-    uint64_t counter = 0;
-    bool sha;
-    Coin(const Digest &seed, bool sha_) : digest(seed), sha(sha_) {}
-    Digest h(const std::vector<uint8_t> &m) const { return sha ? sha256(m.data(), m.size()) : keccak256(m.data(), m.size()); }
-    void reseed_with_bytes(const uint8_t *data, size_t len) {
-        std::vector<uint8_t> m(digest.begin(), digest.end());                  // be32(digest + 1)
-        for (int i = 31; i >= 0; --i) { if (++m[i] != 0) break; }
-        m.insert(m.end(), data, data + len);
-        digest = h(m);
-        counter = 0;
-    }
-    void reseed_with_digest(const Digest &d) { reseed_with_bytes(d.data(), 32); }
-    void reseed_with_fq3s(const uint64_t *vals, size_t n3) {                   // little-endian 8-byte coordinates
-        std::vector<uint8_t> b(8 * n3);
-        for (size_t i = 0; i < n3; ++i) for (int k = 0; k < 8; ++k) b[8 * i + k] = (uint8_t)(vals[i] >> (8 * k));
-        reseed_with_bytes(b.data(), b.size());
-    }
-    void reseed_with_int(uint64_t v) {
-        uint8_t b[8];
-        for (int k = 0; k < 8; ++k) b[k] = (uint8_t)(v >> (8 * (7 - k)));
-        reseed_with_bytes(b, 8);
-    }
-    Digest draw_bytes() {
-        std::vector<uint8_t> m(digest.begin(), digest.end());
-        uint8_t c[32] = {0};
-        for (int k = 0; k < 8; ++k) c[31 - k] = (uint8_t)(counter >> (8 * k));
-        m.insert(m.end(), c, c + 32);
-        ++counter;
-        return h(m);
-    }
-    uint64_t draw_felt() {                                                     // the first of the draw's four big-endian words below p
-        for (;;) {
-            const Digest d = draw_bytes();
-            for (int k = 0; k < 4; ++k) {
-                uint64_t v = 0;
-                for (int j = 0; j < 8; ++j) v = (v << 8) | d[8 * k + j];
-                if (v < P) return v;
-            }
-        }
-    }
-    Fq3 draw_fq3() { Fq3 r; r[0] = draw_felt(); r[1] = draw_felt(); r[2] = draw_felt(); return r; }
-    std::vector<uint64_t> draw_queries(size_t max_n, uint64_t domain) {
-        std::vector<uint64_t> vals;
-        while (vals.size() < max_n) {
-            const Digest d = draw_bytes();
-            for (int k = 0; k < 4 && vals.size() < max_n; ++k) {
-                uint64_t v = 0;
-                for (int j = 0; j < 8; ++j) v = (v << 8) | d[8 * k + j];
-                vals.push_back(v % domain);
-            }
-        }
-        std::sort(vals.begin(), vals.end());
-        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
-        return vals;
-    }
-};
-void be64(std::vector<uint8_t> &b, uint64_t v) { for (int k = 7; k >= 0; --k) b.push_back((uint8_t)(v >> (8 * k))); }
-}  // namespace
-
-Digest transcript_seed(const Digest &seed, const Options &opt, uint64_t trace_len, const Digest &statement_digest) {
-    std::vector<uint8_t> b(seed.begin(), seed.end());
-    for (uint64_t v : {(uint64_t)opt.num_queries, (uint64_t)opt.log_blowup, (uint64_t)opt.grinding, (uint64_t)opt.fold, (uint64_t)opt.max_remainder, trace_len}) be64(b, v);
-    b.insert(b.end(), statement_digest.begin(), statement_digest.end());
-    if (opt.sha256) { const char *name = "sha256"; b.insert(b.end(), name, name + 6); }
-    return keccak256(b.data(), b.size());
-}
+// (mul3, SHA-256, the coin and the transcript seed: gl_transcript.cpp, shared with the verifier)
 
 namespace {
 struct Dev {                                                // a device buffer of the context's pool

@@ -12,6 +12,8 @@
 
 #include "extension.hpp"
 #include "goldilocks_prover.hpp"
+#include "air_plain.hpp"
+#include "goldilocks_verifier.hpp"
 #include "prover.hpp"
 #include "sharded.hpp"
 #include "public_input.hpp"
@@ -861,9 +863,9 @@ gl::CheckBuilder gl_check_builder(ssh_gl_check_cb check_cb, void *user) {
 }
 // the body ssh_gl_prove and ssh_gl_prove_files_device share: the proof for these columns as the u64 blob described above; `extension`
 // makes the extension trace's coordinate columns for the drawn challenges
-void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base, uint32_t nbase,
-                   uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, const gl::ExtensionBuilder &extension,
-                   ssh_gl_program_cb prog_cb, ssh_gl_check_cb check_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+void gl_prove_blob_with(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base, uint32_t nbase,
+                        uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, const gl::ExtensionBuilder &extension,
+                        const gl::ProgramBuilder &program, const gl::CheckBuilder &check, uint64_t **proof_blob, uint64_t *proof_len) {
     {
         gl::Options opt;
         opt.num_queries = options[0]; opt.log_blowup = options[1]; opt.grinding = options[2]; opt.fold = options[3]; opt.max_remainder = options[4];
@@ -874,24 +876,7 @@ void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32
         std::vector<const uint64_t *> base(d_base, d_base + nbase);
         std::vector<std::pair<uint32_t, uint32_t>> cells;
         for (uint32_t j = 0; j < nmask; ++j) cells.push_back({mask[2 * j], mask[2 * j + 1]});
-        auto flat = [](const std::vector<gl::Fq3> &v) { std::vector<uint64_t> o; for (auto &c : v) o.insert(o.end(), c.begin(), c.end()); return o; };
-        const gl::Proof p = gl::prove(ctx, opt, sd, st, base, n, cells, num_challenges, num_ext, extension,
-            [&](const std::vector<gl::Fq3> &ch, const gl::Fq3 &alpha) {
-                const uint64_t *blob = nullptr;
-                uint64_t len = 0;
-                const std::vector<uint64_t> f = flat(ch);
-                if (prog_cb(user, f.data(), (uint32_t)ch.size(), alpha.data(), &blob, &len) != 0 || !blob || len < 5) throw std::runtime_error("program callback failed");
-                gl::ProgramData pd;
-                const uint64_t n_instr = blob[0], n_consts = blob[1], n_tables = blob[3];
-                if (len != 5 + 2 * n_instr + 3 * n_consts + 2 * n_tables) throw std::runtime_error("program callback: blob length");
-                pd.n_slots = (uint32_t)blob[2];
-                pd.d_tables = reinterpret_cast<const uint64_t *>((uintptr_t)blob[4]);
-                const uint64_t *q = blob + 5;
-                for (uint64_t i = 0; i < 2 * n_instr; ++i) pd.code.push_back((uint32_t)*q++);
-                pd.consts.assign(q, q + 3 * n_consts); q += 3 * n_consts;
-                for (uint64_t i = 0; i < 2 * n_tables; ++i) pd.table_desc.push_back((uint32_t)*q++);
-                return pd;
-            }, gl_check_builder(check_cb, user));
+        const gl::Proof p = gl::prove(ctx, opt, sd, st, base, n, cells, num_challenges, num_ext, extension, program, check);
         std::vector<uint64_t> out{p.trace_len, p.pow_nonce, p.has_ext ? 1ull : 0ull, p.fri_layers.size()};
         auto digest = [&](const Digest &d) { uint64_t w[4]; memcpy(w, d.data(), 32); out.insert(out.end(), w, w + 4); };
         digest(p.base_root); digest(p.ext_root); digest(p.comp_root);
@@ -916,6 +901,54 @@ void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32
         *proof_len = out.size();
     }
 }
+// the program callback as a gl::ProgramBuilder: the blob described above, parsed
+gl::ProgramBuilder gl_program_builder(ssh_gl_program_cb prog_cb, void *user) {
+    return [prog_cb, user](const std::vector<gl::Fq3> &ch, const gl::Fq3 &alpha) {
+        auto flat = [](const std::vector<gl::Fq3> &v) { std::vector<uint64_t> o; for (auto &c : v) o.insert(o.end(), c.begin(), c.end()); return o; };
+        const uint64_t *blob = nullptr;
+        uint64_t len = 0;
+        const std::vector<uint64_t> f = flat(ch);
+        if (prog_cb(user, f.data(), (uint32_t)ch.size(), alpha.data(), &blob, &len) != 0 || !blob || len < 5) throw std::runtime_error("program callback failed");
+        gl::ProgramData pd;
+        const uint64_t n_instr = blob[0], n_consts = blob[1], n_tables = blob[3];
+        if (len != 5 + 2 * n_instr + 3 * n_consts + 2 * n_tables) throw std::runtime_error("program callback: blob length");
+        pd.n_slots = (uint32_t)blob[2];
+        pd.d_tables = reinterpret_cast<const uint64_t *>((uintptr_t)blob[4]);
+        const uint64_t *q = blob + 5;
+        for (uint64_t i = 0; i < 2 * n_instr; ++i) pd.code.push_back((uint32_t)*q++);
+        pd.consts.assign(q, q + 3 * n_consts); q += 3 * n_consts;
+        for (uint64_t i = 0; i < 2 * n_tables; ++i) pd.table_desc.push_back((uint32_t)*q++);
+        return pd;
+    };
+}
+void gl_prove_blob(ss_ctx *ctx, const uint32_t options[6], const uint8_t seed[32], const uint8_t statement_digest[32], const uint64_t *const *d_base, uint32_t nbase,
+                   uint64_t n, const uint32_t *mask, uint32_t nmask, uint32_t num_challenges, uint32_t num_ext, const gl::ExtensionBuilder &extension,
+                   ssh_gl_program_cb prog_cb, ssh_gl_check_cb check_cb, void *user, uint64_t **proof_blob, uint64_t *proof_len) {
+    gl_prove_blob_with(ctx, options, seed, statement_digest, d_base, nbase, n, mask, nmask, num_challenges, num_ext, extension, gl_program_builder(prog_cb, user),
+                       gl_check_builder(check_cb, user), proof_blob, proof_len);
+}
+// The plain layout's extension column made in the C++ host (Trace::build_extension_columns, plain/trace.rs:274-330: the memory and the
+// range-check running quotients, two ss_running_product_gl64x3 calls - what goldilocks.plain_extension_on_device does; refused if the
+// range-check product does not close): the three coordinate columns, owned by the call that holds this
+struct PlainExtension {
+    ss_ctx *ctx; uint64_t *col[3] = {nullptr, nullptr, nullptr};
+    ~PlainExtension() { (void)ss_ctx_sync(ctx); for (auto *c : col) if (c) (void)ss_dev_free(ctx, c); }
+    std::vector<const uint64_t *> build(const uint64_t *const d_cols[5], uint64_t n, const std::vector<gl::Fq3> &ch) {
+        enum { NPC = 1, MEMORY = 2, RANGE_CHECK = 3 };
+        auto ok = [](ss_status st) { if (st != SS_OK) throw std::runtime_error(ss_last_error()); };
+        if (ch.size() != 3) throw std::runtime_error("the plain layout draws three challenges");
+        for (auto *&c : col) {
+            if (!c) { void *p = nullptr; ok(ss_dev_alloc(ctx, n * 8, &p)); c = (uint64_t *)p; }
+            ok(ss_dev_zero(ctx, c, n * 8));                           // (rows 3 mod 4 belong to neither product)
+        }
+        const uint64_t *npc = d_cols[NPC], *mem = d_cols[MEMORY], *rc = d_cols[RANGE_CHECK];
+        uint64_t last_rc[3];
+        ok(ss_running_product_gl64x3(ctx, npc, npc + 1, mem, mem + 1, 2, n / 2, ch[0].data(), ch[1].data(), col, 2, 0, nullptr));
+        ok(ss_running_product_gl64x3(ctx, rc, nullptr, rc + 2, nullptr, 4, n / 4, ch[2].data(), nullptr, col, 4, 1, last_rc));
+        if (last_rc[0] != 1 || last_rc[1] || last_rc[2]) throw std::runtime_error("the range-check permutation does not close");
+        return std::vector<const uint64_t *>(col, col + 3);
+    }
+};
 }  // namespace
 // ssh_gl_prove with the trace checked against the AIR before the extension commitment (gl::prove's build_check): a trace that fails
 // ends the call with "trace does not satisfy the AIR: ..."; check_cb = NULL is ssh_gl_prove
@@ -991,10 +1024,6 @@ int ssh_gl_prove_files_device_checked(ss_ctx *ctx, const uint8_t *trace_bin, uin
                                       const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem, uint64_t *const d_cols[5], const uint32_t options[6],
                                       const uint8_t seed[32], const uint8_t statement_digest[32], const uint32_t *mask, uint32_t nmask, ssh_gl_program_cb prog_cb,
                                       ssh_gl_check_cb check_cb, void *user, double *times_out, uint64_t **proof_blob, uint64_t *proof_len) {
-    struct Columns {                                                 // the extension trace's three coordinate columns: this call's own
-        ss_ctx *ctx; uint64_t *col[3] = {nullptr, nullptr, nullptr};
-        ~Columns() { (void)ss_ctx_sync(ctx); for (auto *c : col) if (c) (void)ss_dev_free(ctx, c); }
-    };
     try {
         if (!ctx || !options || !seed || !statement_digest || !d_cols || !mask || !prog_cb || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove_files_device: NULL argument");
         const auto t_start = std::chrono::steady_clock::now();
@@ -1008,23 +1037,9 @@ int ssh_gl_prove_files_device_checked(ss_ctx *ctx, const uint8_t *trace_bin, uin
         plain_base_trace_device(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols);
         const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         const uint64_t n = 16 * n_steps;
-        enum { NPC = 1, MEMORY = 2, RANGE_CHECK = 3 };
-        Columns ext{ctx};
-        auto ok = [](ss_status st) { if (st != SS_OK) throw std::runtime_error(ss_last_error()); };
+        PlainExtension ext{ctx};
         gl_prove_blob(ctx, options, seed, statement_digest, d_cols, 5, n, mask, nmask, 3, 3,
-            [&](const std::vector<gl::Fq3> &ch) {
-                if (ch.size() != 3) throw std::runtime_error("the plain layout draws three challenges");
-                for (auto *&c : ext.col) {
-                    if (!c) { void *p = nullptr; ok(ss_dev_alloc(ctx, n * 8, &p)); c = (uint64_t *)p; }
-                    ok(ss_dev_zero(ctx, c, n * 8));                   // (rows 3 mod 4 belong to neither product)
-                }
-                const uint64_t *npc = d_cols[NPC], *mem = d_cols[MEMORY], *rc = d_cols[RANGE_CHECK];
-                uint64_t last_rc[3];
-                ok(ss_running_product_gl64x3(ctx, npc, npc + 1, mem, mem + 1, 2, n / 2, ch[0].data(), ch[1].data(), ext.col, 2, 0, nullptr));
-                ok(ss_running_product_gl64x3(ctx, rc, nullptr, rc + 2, nullptr, 4, n / 4, ch[2].data(), nullptr, ext.col, 4, 1, last_rc));
-                if (last_rc[0] != 1 || last_rc[1] || last_rc[2]) throw std::runtime_error("the range-check permutation does not close");
-                return std::vector<const uint64_t *>(ext.col, ext.col + 3);
-            }, prog_cb, check_cb, user, proof_blob, proof_len);
+                      [&](const std::vector<gl::Fq3> &ch) { return ext.build(d_cols, n, ch); }, prog_cb, check_cb, user, proof_blob, proof_len);
         if (ss_ctx_sync(ctx) != SS_OK) throw std::runtime_error(ss_last_error());
         if (times_out) { times_out[0] = gen_s; times_out[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
         return 0;
@@ -1036,6 +1051,223 @@ int ssh_gl_prove_files_device(ss_ctx *ctx, const uint8_t *trace_bin, uint64_t tr
                               double *times_out, uint64_t **proof_blob, uint64_t *proof_len) {
     return ssh_gl_prove_files_device_checked(ctx, trace_bin, trace_len, memory_bin, memory_len, n_steps, mem_addresses, mem_values, n_mem, d_cols, options, seed,
                                              statement_digest, mask, nmask, prog_cb, nullptr, user, times_out, proof_blob, proof_len);
+}
+
+// ---- the 64-bit field's claim with the plain AIR lowered HERE (host/air_plain.cpp): no callback of any kind.  An AIR handle is made
+// once per statement - ctx = NULL gives a host-only handle, for verification and for dumping programs - and owns what depends on the
+// trace length only: the code words, the table descriptions and, with a context, the tables on the device.  Per proof only the constant
+// table is filled.  program / execution: the memory segments (begin, stop); the public memory as for ssh_gl_base_trace_device.
+typedef struct ssh_gl_air ssh_gl_air;
+ssh_gl_air *ssh_gl_air_create_plain(ss_ctx *ctx, uint64_t n_steps, uint64_t rc_min, uint64_t rc_max, const uint64_t program[2], const uint64_t execution[2],
+                                    const uint64_t *mem_addresses, const uint64_t *mem_values, uint64_t n_mem) {
+    try {
+        if (!program || !execution || (n_mem && (!mem_addresses || !mem_values))) throw std::runtime_error("ssh_gl_air_create_plain: NULL argument");
+        gl::PlainStatement st;
+        st.n_steps = n_steps; st.rc_min = rc_min; st.rc_max = rc_max;
+        st.program[0] = program[0]; st.program[1] = program[1]; st.execution[0] = execution[0]; st.execution[1] = execution[1];
+        for (uint64_t i = 0; i < n_mem; ++i) st.public_memory.push_back({mem_addresses[i], mem_values[i]});
+        return reinterpret_cast<ssh_gl_air *>(new gl::PlainAir(ctx, st));
+    } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+void ssh_gl_air_destroy(ssh_gl_air *air) { delete reinterpret_cast<gl::PlainAir *>(air); }
+namespace {
+const gl::PlainAir &gl_air_of(const ssh_gl_air *air, const char *who) {
+    if (!air) throw std::runtime_error(std::string(who) + ": NULL argument");
+    return *reinterpret_cast<const gl::PlainAir *>(air);
+}
+std::vector<gl::Fq3> gl_challenges_of(const uint64_t *challenges, uint32_t n) {
+    std::vector<gl::Fq3> ch(n);
+    for (uint32_t i = 0; i < n; ++i) ch[i] = gl::Fq3{challenges[3 * i], challenges[3 * i + 1], challenges[3 * i + 2]};
+    return ch;
+}
+void gl_blob_out(const std::vector<uint64_t> &out, uint64_t **blob, uint64_t *blob_len) {
+    *blob = (uint64_t *)malloc(out.size() * 8 + 8);
+    memcpy(*blob, out.data(), out.size() * 8);
+    *blob_len = out.size();
+}
+gl::Options gl_options_of(const uint32_t options[6]) {
+    gl::Options opt;
+    opt.num_queries = options[0]; opt.log_blowup = options[1]; opt.grinding = options[2]; opt.fold = options[3]; opt.max_remainder = options[4];
+    opt.sha256 = options[5] != 0;
+    return opt;
+}
+// what both prove calls refuse before anything is uploaded or launched: the blow-up, then the FRI geometry
+void gl_refuse_geometry(const uint32_t options[6], uint64_t n) {
+    const gl::Options opt = gl_options_of(options);
+    gl::check_log_blowup(opt.log_blowup);
+    gl::fri_shape(opt, n << opt.log_blowup);
+}
+std::vector<uint32_t> gl_flat_mask(const gl::PlainAir &air) {
+    std::vector<uint32_t> m;
+    for (auto &c : air.mask()) { m.push_back(c.first); m.push_back(c.second); }
+    return m;
+}
+void gl_same_context(const gl::PlainAir &air, ss_ctx *ctx, const char *who) {
+    if (!ctx) throw std::runtime_error(std::string(who) + ": NULL argument");
+    if (air.ctx() != ctx) throw std::runtime_error(std::string(who) + ": the AIR handle was made " + (air.ctx() ? "for another context" : "without a context: it holds no tables on the device"));
+}
+}  // namespace
+// The lowered composition program for these challenges (3 x 3 u64) and this coefficient, as ssh_gl_program_cb's blob (ssh_free):
+// [n_instr, n_consts, n_slots, n_tables, d_tables, code, consts, table_desc]; a handle made without a context has d_tables = 0 and the
+// table values follow the descriptions.
+int ssh_gl_air_program(const ssh_gl_air *air_h, const uint64_t challenges[9], const uint64_t alpha[3], uint64_t **blob, uint64_t *blob_len) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_air_program");
+        if (!challenges || !alpha || !blob || !blob_len) throw std::runtime_error("ssh_gl_air_program: NULL argument");
+        const gl::ProgramData pd = air.program(gl_challenges_of(challenges, 3), gl::Fq3{alpha[0], alpha[1], alpha[2]});
+        std::vector<uint64_t> out{pd.code.size() / 2, pd.consts.size() / 3, pd.n_slots, pd.table_desc.size() / 2, (uint64_t)(uintptr_t)pd.d_tables};
+        out.insert(out.end(), pd.code.begin(), pd.code.end());
+        out.insert(out.end(), pd.consts.begin(), pd.consts.end());
+        out.insert(out.end(), pd.table_desc.begin(), pd.table_desc.end());
+        if (!pd.d_tables) out.insert(out.end(), air.table_values().begin(), air.table_values().end());
+        gl_blob_out(out, blob, blob_len);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// The check program (one SS_OP_CHECK per bare numerator), the domains and the names, as ssh_gl_check_cb's blob (gl_check_blob.hpp; ssh_free)
+int ssh_gl_air_check_program(const ssh_gl_air *air_h, const uint64_t challenges[9], uint64_t **blob, uint64_t *blob_len) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_air_check_program");
+        if (!challenges || !blob || !blob_len) throw std::runtime_error("ssh_gl_air_check_program: NULL argument");
+        const gl::CheckBlob cb = air.check_program(gl_challenges_of(challenges, 3));
+        std::vector<uint64_t> out{cb.code.size() / 2, cb.consts.size() / 3, cb.n_slots, 0, 0, cb.domains.size()};
+        out.insert(out.end(), cb.code.begin(), cb.code.end());
+        out.insert(out.end(), cb.consts.begin(), cb.consts.end());
+        auto text = [&](const std::string &t) {
+            out.push_back(t.size());
+            for (size_t i = 0; i < t.size(); i += 8) {
+                uint64_t w = 0;
+                for (size_t k = 0; k < 8 && i + k < t.size(); ++k) w |= (uint64_t)(unsigned char)t[i + k] << (8 * k);
+                out.push_back(w);
+            }
+        };
+        for (size_t k = 0; k < cb.domains.size(); ++k) {
+            const ss_check_domain &d = cb.domains[k];
+            out.push_back(d.n_num);
+            for (uint32_t j = 0; j < d.n_num; ++j) { out.push_back(d.num[j][0]); out.push_back(d.num[j][1]); }
+            out.push_back(d.n_den);
+            for (uint32_t j = 0; j < d.n_den; ++j) { out.push_back(d.den[j][0]); out.push_back(d.den[j][1]); }
+            text(cb.names[k]); text(cb.domain_names[k]);
+        }
+        gl_blob_out(out, blob, blob_len);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// the mask: the sorted (component column, row offset) cells the constraints read, two u32 per cell into cells_out (room for `capacity`
+// cells; *n_cells = how many there are), and the statement's digest as the transcript absorbs it
+int ssh_gl_air_mask(const ssh_gl_air *air_h, uint32_t *cells_out, uint32_t capacity, uint32_t *n_cells) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_air_mask");
+        if (!n_cells) throw std::runtime_error("ssh_gl_air_mask: NULL argument");
+        *n_cells = (uint32_t)air.mask().size();
+        for (size_t j = 0; cells_out && j < air.mask().size() && j < capacity; ++j) { cells_out[2 * j] = air.mask()[j].first; cells_out[2 * j + 1] = air.mask()[j].second; }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int ssh_gl_air_statement_digest(const ssh_gl_air *air_h, uint8_t digest_out[32]) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_air_statement_digest");
+        if (!digest_out) throw std::runtime_error("ssh_gl_air_statement_digest: NULL argument");
+        memcpy(digest_out, air.statement_digest().data(), 32);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// the transcript's seed for these options (goldilocks.transcript_seed): what the coin starts from
+int ssh_gl_air_transcript_seed(const ssh_gl_air *air_h, const uint32_t options[6], const uint8_t seed[32], uint8_t seed_out[32]) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_air_transcript_seed");
+        if (!options || !seed || !seed_out) throw std::runtime_error("ssh_gl_air_transcript_seed: NULL argument");
+        Digest sd;
+        memcpy(sd.data(), seed, 32);
+        const Digest d = gl::transcript_seed(sd, gl_options_of(options), air.n(), air.statement_digest());
+        memcpy(seed_out, d.data(), 32);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// The proof for five resident base columns of air.n values each: ssh_gl_prove's blob, the extension column built here.  validate != 0:
+// the trace is checked against the AIR before the extension commitment, as ssh_gl_prove_checked does.
+int ssh_gl_prove_air(ss_ctx *ctx, const ssh_gl_air *air_h, const uint32_t options[6], const uint8_t seed[32], const uint64_t *const d_base[5], int validate,
+                     uint64_t **proof_blob, uint64_t *proof_len) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_prove_air");
+        if (!options || !seed || !d_base || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove_air: NULL argument");
+        gl_same_context(air, ctx, "ssh_gl_prove_air");
+        gl_refuse_geometry(options, air.n());
+        const std::vector<uint32_t> mask = gl_flat_mask(air);
+        PlainExtension ext{ctx};
+        gl_prove_blob_with(ctx, options, seed, air.statement_digest().data(), d_base, 5, air.n(), mask.data(), (uint32_t)air.mask().size(), 3, 3,
+                           [&](const std::vector<gl::Fq3> &ch) { return ext.build(d_base, air.n(), ch); },
+                           [&](const std::vector<gl::Fq3> &ch, const gl::Fq3 &alpha) { return air.program(ch, alpha); },
+                           validate ? gl::CheckBuilder([&](const std::vector<gl::Fq3> &ch) { return air.check_program(ch); }) : gl::CheckBuilder(nullptr), proof_blob, proof_len);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// files -> proof with no callback: ssh_gl_prove_files_device's columns (in d_cols), refusals (in its order and words) and proof blob;
+// the step count and the public memory are the handle's.  times_out as there.
+int ssh_gl_prove_files_air(ss_ctx *ctx, const ssh_gl_air *air_h, const uint8_t *trace_bin, uint64_t trace_len, const uint8_t *memory_bin, uint64_t memory_len,
+                           uint64_t *const d_cols[5], const uint32_t options[6], const uint8_t seed[32], int validate, double *times_out, uint64_t **proof_blob,
+                           uint64_t *proof_len) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_prove_files_air");
+        if (!options || !seed || !d_cols || !proof_blob || !proof_len) throw std::runtime_error("ssh_gl_prove_files_air: NULL argument");
+        gl_same_context(air, ctx, "ssh_gl_prove_files_air");
+        const auto t_start = std::chrono::steady_clock::now();
+        gl_refuse_geometry(options, air.n());
+        const gl::PlainStatement &st = air.statement();
+        if (trace_len != 24 * st.n_steps)
+            throw std::runtime_error("ssh_gl_prove_files_air: the AIR handle was made for " + std::to_string(st.n_steps) + " steps, the trace file holds " + std::to_string(trace_len / 24));
+        std::vector<uint64_t> addrs, vals;
+        for (auto &c : st.public_memory) { addrs.push_back(c.first); vals.push_back(c.second); }
+        plain_base_trace_device(ctx, trace_bin, trace_len, memory_bin, memory_len, st.n_steps, addrs.data(), vals.data(), addrs.size(), d_cols);
+        const double gen_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+        const std::vector<uint32_t> mask = gl_flat_mask(air);
+        PlainExtension ext{ctx};
+        gl_prove_blob_with(ctx, options, seed, air.statement_digest().data(), d_cols, 5, air.n(), mask.data(), (uint32_t)air.mask().size(), 3, 3,
+                           [&](const std::vector<gl::Fq3> &ch) { return ext.build(d_cols, air.n(), ch); },
+                           [&](const std::vector<gl::Fq3> &ch, const gl::Fq3 &alpha) { return air.program(ch, alpha); },
+                           validate ? gl::CheckBuilder([&](const std::vector<gl::Fq3> &ch) { return air.check_program(ch); }) : gl::CheckBuilder(nullptr), proof_blob, proof_len);
+        if (ss_ctx_sync(ctx) != SS_OK) throw std::runtime_error(ss_last_error());
+        if (times_out) { times_out[0] = gen_s; times_out[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// ssh_gl_check_trace's report without a callback: d_cols = the five base columns then the three coordinate columns of the extension trace
+int ssh_gl_check_trace_air(ss_ctx *ctx, const ssh_gl_air *air_h, const uint64_t *const *d_cols, uint32_t ncols, uint32_t log_n, const uint64_t *challenges,
+                           uint32_t nchallenges, uint32_t *n_failures, char **report) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_check_trace_air");
+        if (!ctx || !d_cols || !challenges || !n_failures) throw std::runtime_error("ssh_gl_check_trace_air: NULL argument");
+        if (ncols != 8) throw std::runtime_error("ssh_gl_check_trace_air: " + std::to_string(ncols) + " columns for an AIR of 5 base and 3 extension coordinate columns");
+        if (log_n != air.log_n())
+            throw std::runtime_error("ssh_gl_check_trace_air: the AIR handle was made for a trace of " + std::to_string(air.n()) + " rows, the columns hold " + std::to_string(1ull << (log_n & 63)));
+        if (nchallenges != 3) throw std::runtime_error("the plain layout draws three challenges");
+        const std::vector<gl::ConstraintFailure> bad = gl::check_trace(ctx, air.check_program(gl_challenges_of(challenges, 3)), std::vector<const uint64_t *>(d_cols, d_cols + ncols), log_n);
+        *n_failures = (uint32_t)bad.size();
+        if (report) {
+            std::string text;
+            for (auto &b : bad) text += std::to_string(b.index) + "\t" + b.name + "\t" + b.domain + "\t" + std::to_string(b.first_row) + "\t" + std::to_string(b.count) + "\n";
+            *report = (char *)malloc(text.size() + 1);
+            memcpy(*report, text.c_str(), text.size() + 1);
+        }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// `claim.verify` for this field (cli/src/main.rs:168-178; host/goldilocks_verifier.cpp, the mirror of goldilocks.verify): the proof blob
+// of the prove calls above against the handle's statement (a host-only handle will do).  The blob is untrusted.  -> 0 and the query
+// positions (room for `capacity`; *n_positions = how many), or 1 and the failed check in ssh_last_error.
+int ssh_gl_verify(const ssh_gl_air *air_h, const uint32_t options[6], const uint8_t seed[32], const uint64_t *proof_blob, uint64_t proof_len,
+                  uint32_t required_security_bits, uint64_t *positions_out, uint32_t capacity, uint32_t *n_positions) {
+    try {
+        const gl::PlainAir &air = gl_air_of(air_h, "ssh_gl_verify");
+        if (!options || !seed || !proof_blob) throw std::runtime_error("ssh_gl_verify: NULL argument");
+        Digest sd;
+        memcpy(sd.data(), seed, 32);
+        const gl::Proof proof = gl::parse_proof_blob(proof_blob, proof_len);
+        const std::vector<uint64_t> pos = gl::verify(air, gl_options_of(options), options[5], sd, proof, required_security_bits);
+        if (n_positions) *n_positions = (uint32_t)pos.size();
+        for (size_t i = 0; positions_out && i < pos.size() && i < capacity; ++i) positions_out[i] = pos[i];
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }
 
 static std::vector<Felt> felts_of_challenges(const uint64_t *challenges, uint32_t nchallenges) {

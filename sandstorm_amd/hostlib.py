@@ -830,6 +830,242 @@ def gl_prove_files(ctx, air, options, seed, trace_bin: bytes, memory_bin: bytes,
     return _gl_proof_of_blob(w, opt), {"trace_gen_s": times[0], "total_s": times[1]}
 
 
+# ---- the plain AIR lowered in the C++ host (host/air_plain.cpp): the 64-bit field's claim with no callback ---------------------------
+class GlPlainAir:
+    """An AIR handle of the C++ host for the plain layout over the 64-bit field (host_capi.cpp ssh_gl_air_create_plain): the mirror of
+    layouts/plain.py for the statement `pi`, lowered once.  ctx = None: a host-only handle (gl_verify, .program, .check_program, .mask);
+    with a backend.Context the handle owns the zerofier tables on that context's device and serves gl_prove_air / gl_prove_files_air /
+    gl_check_trace_air."""
+
+    def __init__(self, ctx, pi):
+        h = load()
+        u64p = C.POINTER(C.c_uint64)
+        h.ssh_gl_air_create_plain.restype = C.c_void_p
+        h.ssh_gl_air_create_plain.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, C.c_uint64]
+        h.ssh_gl_air_destroy.argtypes = [C.c_void_p]
+        h.ssh_gl_air_destroy.restype = None
+        prog, exe = pi.memory_segments["program"], pi.memory_segments["execution"]
+        addrs = np.array([a for a, _ in pi.public_memory], dtype=np.uint64)
+        vals = np.array([int(v) for _, v in pi.public_memory], dtype=np.uint64)
+        self.ctx, self.pi, self.n = ctx, pi, 16 * int(pi.n_steps)
+        self.handle = h.ssh_gl_air_create_plain(ctx.handle if ctx is not None else None, int(pi.n_steps), int(pi.rc_min), int(pi.rc_max), (C.c_uint64 * 2)(*prog),
+                                                (C.c_uint64 * 2)(*exe), addrs.ctypes.data_as(u64p), vals.ctypes.data_as(u64p), len(addrs))
+        if not self.handle:
+            raise _lib.SandstormHipError("host: " + h.ssh_last_error().decode())
+
+    def close(self):
+        """frees the handle and its tables on the device.  A handle that outlives its context is dropped, not freed: its tables went
+        with the context's pool, and the destructor must not touch a context that is gone"""
+        if getattr(self, "handle", None):
+            if self.ctx is None or self.ctx.handle:
+                load().ssh_gl_air_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _fq3s(values):
+        a = np.ascontiguousarray([[int(v) for v in c] for c in values], dtype=np.uint64).reshape(-1)
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    def _blob(self, fn, *args):
+        out, ln = C.POINTER(C.c_uint64)(), C.c_uint64()
+        _check(fn(self.handle, *args, C.byref(out), C.byref(ln)))
+        w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
+        load().ssh_free(out)
+        return w
+
+    def program_blob(self, challenges, alpha):
+        """ssh_gl_air_program's blob as it comes (hostlib._gl_program_callback's format; the table values follow for a host-only handle)"""
+        fn = load().ssh_gl_air_program
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+        (keep_c, ch), (keep_a, al) = self._fq3s(challenges), self._fq3s([alpha])
+        return self._blob(fn, ch, al)
+
+    def program(self, challenges, alpha):
+        """the lowered composition program for these challenges and this coefficient -> {"code": uint32 words, "consts": [k, 3] uint64,
+        "n_slots", "table_desc": [offset, log2 length, ...], "d_tables": device address or 0, "tables": the table values (host-only handle)
+        or None}: what air_program.lower(layouts.plain.composition(...), ext=True) and Tables.device_tables() give"""
+        w = self.program_blob(challenges, alpha)
+        n_instr, n_consts, n_slots, n_tables, d_tables = (int(v) for v in w[:5])
+        o = 5
+        code = w[o:o + 2 * n_instr].astype(np.uint32)
+        o += 2 * n_instr
+        consts = w[o:o + 3 * n_consts].reshape(-1, 3).copy()
+        o += 3 * n_consts
+        tdesc = [int(v) for v in w[o:o + 2 * n_tables]]
+        o += 2 * n_tables
+        return {"code": code, "consts": consts, "n_slots": n_slots, "table_desc": tdesc, "d_tables": d_tables, "tables": w[o:].copy() if not d_tables else None}
+
+    def check_program_blob(self, challenges):
+        """ssh_gl_air_check_program's blob (gl_check_blob's format)"""
+        fn = load().ssh_gl_air_check_program
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+        keep, ch = self._fq3s(challenges)
+        return self._blob(fn, ch)
+
+    def check_program(self, challenges):
+        """-> {"code", "consts", "n_slots", "domains": [(num, den)], "names", "domain_names"}: layouts.plain.check_program's parts"""
+        w = [int(v) for v in self.check_program_blob(challenges)]
+        n_instr, n_consts, n_slots, n_tables, _, n_checks = w[:6]
+        o = 6
+        code = np.array(w[o:o + 2 * n_instr], dtype=np.uint32)
+        o += 2 * n_instr
+        consts = np.array(w[o:o + 3 * n_consts], dtype=np.uint64).reshape(-1, 3)
+        o += 3 * n_consts + 2 * n_tables
+        domains, names, domain_names = [], [], []
+
+        def text():
+            nonlocal o
+            nbytes = w[o]
+            words = (nbytes + 7) // 8
+            b = b"".join(v.to_bytes(8, "little") for v in w[o + 1:o + 1 + words])[:nbytes]
+            o += 1 + words
+            return b.decode()
+        for _ in range(n_checks):
+            sides = []
+            for _side in range(2):
+                cnt = w[o]
+                sides.append([(w[o + 1 + 2 * j], w[o + 2 + 2 * j]) for j in range(cnt)])
+                o += 1 + 2 * cnt
+            domains.append(tuple(sides))
+            names.append(text())
+            domain_names.append(text())
+        assert o == len(w)
+        return {"code": code, "consts": consts, "n_slots": n_slots, "domains": domains, "names": names, "domain_names": domain_names}
+
+    @property
+    def mask(self):
+        fn = load().ssh_gl_air_mask
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+        cnt = C.c_uint32()
+        _check(fn(self.handle, None, 0, C.byref(cnt)))
+        cells = (C.c_uint32 * (2 * cnt.value))()
+        _check(fn(self.handle, cells, cnt.value, C.byref(cnt)))
+        return [(int(cells[2 * j]), int(cells[2 * j + 1])) for j in range(cnt.value)]
+
+    def statement_digest(self):
+        fn = load().ssh_gl_air_statement_digest
+        fn.argtypes = [C.c_void_p, C.c_char_p]
+        out = C.create_string_buffer(32)
+        _check(fn(self.handle, out))
+        return out.raw
+
+    def transcript_seed(self, seed, options):
+        fn = load().ssh_gl_air_transcript_seed
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p]
+        out = C.create_string_buffer(32)
+        _check(fn(self.handle, _gl_options(options), bytes(seed), out))
+        return out.raw
+
+
+def _gl_options(opt):
+    """goldilocks.Options as the six u32 the C entry points take; a hash the library does not know travels as 2 and is refused there"""
+    return (C.c_uint32 * 6)(opt.num_queries, opt.log_blowup, opt.grinding, opt.fold, opt.max_remainder, {"blake2s": 0, "sha256": 1}.get(opt.hash, 2))
+
+
+def gl_prove_air(ctx, air: GlPlainAir, options, seed, base_cols, validate=False):
+    """the 64-bit field's claim for five resident base columns by the C++ host alone (host_capi.cpp ssh_gl_prove_air): the extension
+    column, the lowered composition program and, with validate, the check program are made there.  -> goldilocks.Proof, the one gl_prove
+    and goldilocks.Prover write"""
+    from . import goldilocks as gs
+    opt = options or gs.Options()
+    if len(base_cols) != 5:
+        raise _lib.SandstormHipError("host: %d device columns for a layout of 5" % len(base_cols))
+    n = int(base_cols[0].shape[0]) if hasattr(base_cols[0], "shape") else int(base_cols[0].nbytes // 8)
+    if n != air.n:
+        raise _lib.SandstormHipError("host: the AIR handle was made for a trace of %d rows, the columns hold %d" % (air.n, n))
+    fn = load().ssh_gl_prove_air
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    out, ln = C.POINTER(C.c_uint64)(), C.c_uint64()
+    _check(fn(ctx.handle, air.handle, _gl_options(opt), bytes(seed), be._ptr_array(base_cols), 1 if validate else 0, C.byref(out), C.byref(ln)))
+    w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
+    load().ssh_free(out)
+    return _gl_proof_of_blob(w, opt)
+
+
+def gl_prove_files_air(ctx, air: GlPlainAir, options, seed, trace_bin: bytes, memory_bin: bytes, dev_cols, validate=False):
+    """files -> proof with no callback of any kind (host_capi.cpp ssh_gl_prove_files_air): gl_prove_files with the plain AIR lowered by
+    the C++ host.  -> (goldilocks.Proof, {"trace_gen_s", "total_s"})"""
+    from . import goldilocks as gs
+    opt = options or gs.Options()
+    if len(dev_cols) != 5:
+        raise _lib.SandstormHipError("host: %d device columns for a layout of 5" % len(dev_cols))
+    if len(trace_bin) % 24:
+        raise _lib.SandstormHipError("host: trace file is not a sequence of (ap, fp, pc) u64 triples")
+    fn = load().ssh_gl_prove_files_air
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_char_p, C.c_int,
+                   C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    out, ln, times = C.POINTER(C.c_uint64)(), C.c_uint64(), (C.c_double * 2)()
+    _check(fn(ctx.handle, air.handle, bytes(trace_bin), len(trace_bin), bytes(memory_bin), len(memory_bin), be._ptr_array(dev_cols), _gl_options(opt), bytes(seed),
+              1 if validate else 0, times, C.byref(out), C.byref(ln)))
+    w = np.ctypeslib.as_array(out, shape=(ln.value,)).copy()
+    load().ssh_free(out)
+    return _gl_proof_of_blob(w, opt), {"trace_gen_s": times[0], "total_s": times[1]}
+
+
+def gl_check_trace_air(ctx, air: GlPlainAir, cols, challenges):
+    """gl_check_trace with the check program made by the C++ host (host_capi.cpp ssh_gl_check_trace_air) -> [(index, name, domain,
+    first_row, count)], goldilocks.check_trace's report"""
+    n = int(cols[0].shape[0]) if hasattr(cols[0], "shape") else int(cols[0].nbytes // 8)
+    ch = np.ascontiguousarray([[int(v) for v in c] for c in challenges], dtype=np.uint64).reshape(-1)
+    fn = load().ssh_gl_check_trace_air
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
+    n_bad, report = C.c_uint32(), C.c_void_p()
+    _check(fn(ctx.handle, air.handle, be._ptr_array(cols), len(cols), n.bit_length() - 1, ch.ctypes.data_as(C.POINTER(C.c_uint64)), len(challenges), C.byref(n_bad),
+              C.byref(report)))
+    text = C.string_at(report.value).decode() if report.value else ""
+    load().ssh_free(report)
+    out = []
+    for line in text.splitlines():
+        index, name, domain, first_row, count = line.split("\t")
+        out.append((int(index), name, domain, int(first_row), int(count)))
+    assert len(out) == n_bad.value
+    return out
+
+
+def gl_blob_of_proof(proof):
+    """goldilocks.Proof -> the u64 proof blob of ssh_gl_prove* (the inverse of _gl_proof_of_blob), as ssh_gl_verify reads it.  The arrays
+    go in with the shapes they have: a malformed proof makes a malformed blob"""
+    u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+    digest = lambda d: np.frombuffer(bytes(d).ljust(32, b"\0")[:32], dtype=np.uint64)
+    has_ext = proof.ext is not None
+    parts = [np.array([int(proof.trace_len), int(proof.pow_nonce), 1 if has_ext else 0, len(proof.fri_layers)], dtype=np.uint64),
+             digest(proof.base_root), digest(proof.ext_root or bytes(32)), digest(proof.comp_root),
+             np.array([len(proof.ood_trace)], dtype=np.uint64), u64(proof.ood_trace), u64(proof.ood_comp),
+             np.array([len(proof.remainder)], dtype=np.uint64), u64(proof.remainder)]
+    for fl in proof.fri_layers:
+        parts += [digest(fl.root), np.array([fl.log_len], dtype=np.uint64)]
+
+    def opening(op):
+        rows, paths = np.asarray(op.rows), np.asarray(op.paths)
+        return [np.array([rows.shape[0], rows.shape[1] if rows.ndim > 1 else 0, paths.shape[1] if paths.ndim > 1 else 0], dtype=np.uint64), u64(rows),
+                np.ascontiguousarray(paths, dtype=np.uint8).reshape(-1).view(np.uint64)]
+    for op in [proof.base] + ([proof.ext] if has_ext else []) + [proof.comp] + [fl.opening for fl in proof.fri_layers]:
+        parts += opening(op)
+    return np.concatenate(parts)
+
+
+def gl_verify_blob(air: GlPlainAir, options, seed, blob, required_security_bits=80):
+    """ssh_gl_verify on a raw u64 blob (untrusted) -> the query positions; SandstormHipError names the failed check"""
+    blob = np.ascontiguousarray(blob, dtype=np.uint64)
+    fn = load().ssh_gl_verify
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]
+    pos, cnt = (C.c_uint64 * 256)(), C.c_uint32()
+    _check(fn(air.handle, _gl_options(options), bytes(seed), blob.ctypes.data_as(C.POINTER(C.c_uint64)), len(blob), int(required_security_bits), pos, 256, C.byref(cnt)))
+    return [int(pos[i]) for i in range(cnt.value)]
+
+
+def gl_verify(air: GlPlainAir, proof, seed, required_security_bits=80):
+    """goldilocks.verify by the C++ host (host/goldilocks_verifier.cpp through ssh_gl_verify): the proof against the handle's statement
+    under the proof's own options -> the query positions; a refusal is a SandstormHipError whose text is goldilocks.VerificationError's"""
+    return gl_verify_blob(air, proof.options, seed, gl_blob_of_proof(proof), required_security_bits)
+
+
 _INSTANCE_SHAPES = (("pedersen", 9), ("range_check", 5), ("ecdsa", 17), ("bitwise", 9), ("ec_op", 21), ("poseidon", 13))
 COLUMN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
